@@ -3,6 +3,7 @@
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c3|c4|c5|c5s|c2t|c1]
                     [--scaling weak|strong] [--also auto|none|c3,c4,...] [--share-of K [--share-rank R]]
+                    [--dump-outputs DIR]
 
 A "step" is one pass of the hot path over one batch of synthetic queries against the
 HBM-resident synthetic database (k-mer pack + MurmurHash3 + row gather + AND/count + hit
@@ -48,6 +49,12 @@ The CPU baseline (rank 0, N=1 only) times the REFERENCE binary (oracle/_ref/kwag
 <=2048-column .db files) when it travelled with the snapshot, else the repo's C restatement, on
 a bounded column subset of the same workload.  It is a reported baseline, not the target.
 
+--dump-outputs DIR: after the timed region, what the headline's LAST timed step returned to its caller goes to
+DIR/<name>.npy as float64 (hits [N, 3] = query, column, num_match; num_query_kmer and query_threshold per query; a
+sharded run: rank 0's merged list), at most 64 MB in all (longer hit lists: a fixed seeded sample of rows, the row
+numbers beside them).  The inputs are seeded: the same arguments give the same inputs, so two builds can be compared
+file for file.  The line then carries `dump_outputs` (directory, shapes, what was sampled).
+
 Rank 0 prints the result as ONE JSON line, the last line of stdout (with NCCL_DEBUG=VERSION in the
 environment RCCL prints its version banner to stdout before it).
 """
@@ -67,6 +74,7 @@ sys.path.insert(0, ROOT)
 HBM_PEAK_GBPS = 8000.0   # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 SUSTAINED_SECONDS = 2.0  # back-to-back steps after the timed region (DVFS: a 40 ms window could be a burst)
 MULTI_GROUPS = {"c5": "C5_GROUPS", "c5tiny": "C5_TEST_GROUPS"}     # workloads of several filter-size groups (kwage_amd/synth.py)
+DUMP_BYTES = 64_000_000  # --dump-outputs: all arrays together (.npy headers aside); longer hit lists are sampled
 
 
 def parse_args(argv=None):
@@ -89,7 +97,14 @@ def parse_args(argv=None):
     ap.add_argument("--early-exit", action="store_true", help="enable the reference's early exit for the WHOLE run (not the nominal figure; the PMC passes behind the `early_exit` blocks use it)")
     ap.add_argument("--no-early-exit-block", action="store_true", help="skip the `early_exit` block (the same batch searched with the reference's early exit, after the timed region)")
     ap.add_argument("--cpu-files", type=int, default=0, help="number of 2048-column .db files of the CPU sample (default: host cores, max 16)")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the headline's last timed step returned as DIR/<name>.npy (float64, at most %d bytes in all)" % DUMP_BYTES)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return args
 
 
 # ------------------------------------------------------------------------------------------------------
@@ -575,6 +590,54 @@ def early_exit_block(args, name, members, s, threshold, flags, nominal, pmc_appl
 
 
 # ------------------------------------------------------------------------------------------------------
+# --dump-outputs: what the timed path returned in its last timed step, for comparing two builds output for output
+# ------------------------------------------------------------------------------------------------------
+def step_outputs(results, merged):
+    """-> {name: float64 array} of one step.  Single-GPU: per group the SearchResult's hit list [N, 3] (query, column,
+    num_match; sorted by query, column) and its per-query num_query_kmer / query_threshold.  Sharded: rank 0's merged hit
+    list(s) [N, 3] with global column numbers.  Several groups or lists: names carry a "group<i>_" prefix."""
+    import numpy as np
+    out = {}
+    if results:
+        for gi, r in enumerate(results):
+            pre = "" if len(results) == 1 else "group%d_" % gi
+            h = r.hits
+            out[pre + "hits"] = np.stack([h["query"], h["column"], h["num_match"]], axis=1).astype(np.float64)
+            out[pre + "num_query_kmer"] = np.asarray(r.num_query_kmer, dtype=np.float64)
+            out[pre + "query_threshold"] = np.asarray(r.query_threshold, dtype=np.float64)
+    else:
+        for gi, m in enumerate(merged):
+            pre = "" if len(merged) == 1 else "group%d_" % gi
+            out[pre + "hits"] = np.asarray(m if m is not None else np.zeros((0, 3)), dtype=np.float64).reshape(-1, 3)
+    return out
+
+
+def write_outputs(dirname, arrays, budget=DUMP_BYTES, seed=0):
+    """Write `arrays` as dirname/<name>.npy.  When everything would exceed `budget` bytes, every hit list keeps a fixed,
+    seeded sample of its rows (sorted; the same rows for the same list length) in proportion to its size, and the row
+    numbers kept go beside it as <name>_sample_rows.npy.  -> what was written."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    lists = [n for n in arrays if n.endswith("hits")]
+    fixed = sum(a.nbytes for n, a in arrays.items() if n not in lists)
+    listed = sum(arrays[n].nbytes for n in lists)
+    room = max(budget - fixed, 0)
+    info = {"dir": os.path.abspath(dirname), "files": {}, "sampled": {}}
+    for name in sorted(arrays):
+        a = arrays[name]
+        if name in lists and listed > room:
+            # a kept row costs its 3 values plus its row number
+            keep = min(len(a), int(room * a.nbytes // listed) // (a.itemsize * (a.shape[1] + 1)))
+            rows = np.sort(np.random.default_rng(seed).choice(len(a), size=keep, replace=False))
+            np.save(os.path.join(dirname, name + "_sample_rows.npy"), rows.astype(np.float64))
+            info["sampled"][name] = {"rows": int(len(a)), "kept": int(keep), "seed": seed}
+            a = a[rows]
+        np.save(os.path.join(dirname, name + ".npy"), a)
+        info["files"][name] = list(a.shape)
+    return info
+
+
+# ------------------------------------------------------------------------------------------------------
 # one rank
 # ------------------------------------------------------------------------------------------------------
 class Env:
@@ -625,15 +688,20 @@ def measure(env, args, name, headline, force_scaling=None):
         ss = [ShardedSearch(dist, rank, world, int(m.group.column_span), device_tensor_search_fn(m.group, flags, dev), device=cdev)
               for m in members]
 
+    last_merged = []          # sharded: what rank 0 received in the last step (one list, or one per group without the pipeline)
+
     def step():
         """One synchronous pass of the hot path; returns (results-or-None, search_kernel_ms, hits delivered to rank 0)."""
         if not sharded:
             rs = [m.group.search(s.batch, threshold, flags) for m in members]
             return rs, sum(r.search_kernel_ms for r in rs), sum(len(r.hits) for r in rs)
         total = 0
+        lists = []
         for one in ss:          # one group after the other; each ends in ONE gatherv of its hit list
             merged, _ = one.search(s.batch, threshold)
             total += len(merged) if merged is not None else 0
+            lists.append(merged)
+        last_merged[:] = lists
         return None, 0.0, total
 
     def sync_all():
@@ -744,6 +812,7 @@ def measure(env, args, name, headline, force_scaling=None):
                 if i + 2 < nsteps:
                     pipe.begin(s.batch, threshold)
                 merged = hx.exchange_step(buf, n)
+            last_merged[:] = [merged]
             nhits = len(merged) if merged is not None else 0
         elif not sharded:
             # The searches of all steps, group after group, stream through the two search slots of the context: search
@@ -794,6 +863,8 @@ def measure(env, args, name, headline, force_scaling=None):
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
     timed_kernel_ms = list(kernel_ms)
+    # what the last timed step returned (headline, rank 0), taken before the sustained block repeats the steps
+    dumped = step_outputs(list(last_results), list(last_merged)) if (headline and args.dump_outputs and rank == 0) else None
 
     # ---- sustained block: the same steps back to back for >= SUSTAINED_SECONDS (the count is derived from the agreed
     # max-over-ranks step time, so every rank runs the same number of steps and collectives) ------------------------
@@ -944,6 +1015,8 @@ def measure(env, args, name, headline, force_scaling=None):
             rcheck["ranks_ok"] = [bool(r[8] == 1.0) for r in per_rank]
             rcheck["checked"] = "rank-local hit lists of the kernel that was timed (%s), after the timed region" % kernel
             out["result_check"] = rcheck
+        if dumped is not None:
+            out["dump_outputs"] = write_outputs(args.dump_outputs, dumped)
         if force_sharded:
             out["config"]["note"] = "KWAGE_BENCH_FORCE_SHARDED: multi-GPU code path on one rank"
         if headline and world == 1 and not args.no_cpu_baseline:

@@ -254,3 +254,81 @@ def test_result_check_accepts_the_oracles_lists_and_refuses_anything_else(oracle
         for bad in (dropped, altered, added):
             if bad is not None:
                 assert not bench.result_check([member], [mk(bad)], thr)["ok"]
+
+
+def test_steps_and_warmup_are_validated():
+    import bench
+    a = bench.parse_args(["--steps", "7", "--warmup", "0"])
+    assert a.steps == 7 and a.warmup == 0 and a.dump_outputs is None
+    for argv in (["--steps", "0"], ["--steps", "-3"], ["--warmup", "-1"]):
+        with pytest.raises(SystemExit):
+            bench.parse_args(argv)
+
+
+def test_dump_outputs_writes_float64_arrays_within_the_budget(tmp_path):
+    """step_outputs + write_outputs: a step's SearchResults become float64 .npy files; over the budget every hit list
+    keeps the same seeded rows (row numbers beside them), the per-query arrays stay whole."""
+    import numpy as np
+    import bench
+    from kwage_amd.engine import HIT_DTYPE, SearchResult
+    rng = np.random.default_rng(3)
+    n = 5000
+    hits = np.zeros(n, dtype=HIT_DTYPE)
+    hits["query"] = np.sort(rng.integers(0, 100, n))
+    hits["column"] = rng.integers(0, 1 << 32, n, dtype=np.uint64)
+    hits["num_match"] = rng.integers(0, 1000, n)
+    nk = rng.integers(0, 1000, 100).astype(np.uint32)
+    res = SearchResult(hits, nk, nk // 2, int(nk.sum()), 0, 0, 0.0, 0.0, 1, "stub")
+    arrays = bench.step_outputs([res], [])
+    assert sorted(arrays) == ["hits", "num_query_kmer", "query_threshold"] and all(a.dtype == np.float64 for a in arrays.values())
+    assert np.array_equal(arrays["hits"][:, 1], hits["column"].astype(np.float64))      # uint32 values survive exactly
+    whole = bench.write_outputs(str(tmp_path / "whole"), arrays)
+    assert whole["sampled"] == {} and whole["files"]["hits"] == [n, 3]
+    assert np.array_equal(np.load(tmp_path / "whole" / "hits.npy"), arrays["hits"])
+    budget = 2 * nk.nbytes + 64 * 1024
+    small = [bench.write_outputs(str(tmp_path / d), arrays, budget=budget) for d in ("a", "b")]
+    assert small[0] == dict(small[1], dir=small[0]["dir"])
+    kept = small[0]["sampled"]["hits"]["kept"]
+    assert 0 < kept < n and sum(os.path.getsize(p) for p in (tmp_path / "a").iterdir()) <= budget + 4 * 128
+    rows = np.load(tmp_path / "a" / "hits_sample_rows.npy")
+    assert np.array_equal(np.load(tmp_path / "a" / "hits.npy"), arrays["hits"][rows.astype(np.int64)])
+    assert np.array_equal(np.load(tmp_path / "a" / "num_query_kmer.npy"), nk.astype(np.float64))
+    for name in ("hits", "hits_sample_rows", "num_query_kmer", "query_threshold"):
+        assert np.array_equal(np.load(tmp_path / "a" / (name + ".npy")), np.load(tmp_path / "b" / (name + ".npy")))
+    # a sharded step: rank 0's merged int64 [N, 3] list(s)
+    two = bench.step_outputs([], [np.arange(6, dtype=np.int64).reshape(2, 3), None])
+    assert sorted(two) == ["group0_hits", "group1_hits"] and two["group1_hits"].shape == (0, 3)
+
+
+@pytest.mark.gpu
+def test_bench_dumps_what_its_last_timed_step_returned(tmp_path):
+    """--dump-outputs on the GPU: the files hold exactly what one search of the same seeded batch returns, the same from
+    run to run, and --steps is the number of timed steps the line reports."""
+    import numpy as np
+    import kwage_amd as ka
+    from kwage_amd import synth
+    lines = []
+    for d in ("one", "two"):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--workload", "tiny", "--no-cpu-baseline",
+                            "--no-sustained", "--no-early-exit-block", "--also", "none", "--dump-outputs", str(tmp_path / d)],
+                           capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines.append(json.loads(r.stdout.strip().splitlines()[-1]))
+    line = lines[0]
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["result_check"]["ok"]
+    assert line["dump_outputs"]["sampled"] == {} and line["dump_outputs"]["files"]["hits"] == [line["config"]["hits_per_step"], 3]
+    names = sorted(p.name for p in (tmp_path / "one").iterdir())
+    assert names == ["hits.npy", "num_query_kmer.npy", "query_threshold.npy"]
+    for name in names:
+        assert np.array_equal(np.load(tmp_path / "one" / name), np.load(tmp_path / "two" / name)), name
+    w = synth.WORKLOADS["tiny"]
+    with ka.Context(0) as ctx:
+        s = synth.build(ctx, w, seed=1, column_seed=0)
+        res = s.group.search(s.batch, w.threshold, ka.SEARCH_TIMING)
+        s.batch.close()
+        s.group.close()
+    hits = np.load(tmp_path / "one" / "hits.npy")
+    assert hits.dtype == np.float64 and len(hits) > 0
+    assert np.array_equal(hits, np.stack([res.hits["query"], res.hits["column"], res.hits["num_match"]], axis=1).astype(np.float64))
+    assert np.array_equal(np.load(tmp_path / "one" / "num_query_kmer.npy"), res.num_query_kmer.astype(np.float64))
+    assert np.array_equal(np.load(tmp_path / "one" / "query_threshold.npy"), res.query_threshold.astype(np.float64))
