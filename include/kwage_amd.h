@@ -233,6 +233,22 @@ int kwage_search(kwage_group *g, kwage_batch *b, float threshold, uint32_t flags
                  kwage_result **out);
 void kwage_result_free(kwage_result *r);
 
+/* Top-k search, with no counterpart in the reference: for every query, the k best-scoring columns of the group.
+ *   - a column's score is its num_match: what kwage_search reports for it at a threshold whose floor is f below;
+ *   - per query with n distinct k-mers the floor is f = kwage_query_threshold(threshold, n); eligible are the real
+ *     columns with score >= f (pad bits never count); threshold 0 means "the k best, whatever their score";
+ *   - the selection is the first min(k, #eligible) eligible columns under the key (score descending, column
+ *     ascending); across files or groups a host merges under (score descending, file order, column ascending);
+ *   - a query without k-mers (n = 0) has no hits;
+ *   - 1 <= k <= KWAGE_TOPK_MAX and 0 <= threshold <= 1, else KWAGE_ERR_ARG.
+ * The result is a kwage_result, freed with kwage_result_free; its records are ordered by (query, column) like every
+ * other result, query_threshold = the floor f (n at threshold 1), search_kernel names the kernels that ran,
+ * KWAGE_SEARCH_TIMING / _TIMING_KMER are honoured.  KWAGE_SEARCH_EARLY_EXIT is ignored: every tile is counted to
+ * the end (no exact bound is kept across tiles).  Synchronous; runs on the context's first stream. */
+#define KWAGE_TOPK_MAX 1024u
+int kwage_search_topk(kwage_group *g, kwage_batch *b, uint32_t k, float threshold, uint32_t flags,
+                      kwage_result **out);
+
 /* The same search in two halves, for hosts that stream many batches: submit enqueues the whole device
  * pipeline and returns at once; collect waits for it and builds the result.  A context holds at most TWO
  * pending searches (each on its own HIP stream), so the k-mer stage, copy-back and host post-processing

@@ -20,6 +20,8 @@ SEARCH_EARLY_EXIT = 1
 SEARCH_TIMING = 2
 SEARCH_TIMING_KMER = 4
 
+TOPK_MAX = native.TOPK_MAX
+
 HIT_DTYPE = np.dtype([("query", "<u4"), ("column", "<u4"), ("num_match", "<u4")])
 
 
@@ -284,6 +286,15 @@ def search(group: Group, batch: Batch, threshold: float, flags: int = 0) -> Sear
     return _unpack_result(res)
 
 
+def search_topk(group: Group, batch: Batch, k: int, threshold: float = 0.0, flags: int = 0) -> SearchResult:
+    """kwage_search_topk(): for every query, the k best-scoring columns of the group -- score = num_match, eligible the
+    columns with score >= the floor (unsigned)(threshold * n), ordered by (score descending, column ascending) and cut at
+    k.  Hits come back ordered by (query, column) like every other result; query_threshold holds the floor."""
+    res = C.POINTER(native.Result)()
+    check(lib().kwage_search_topk(group._h, batch._h, min(max(int(k), 0), 0xFFFFFFFF), C.c_float(threshold), flags, C.byref(res)))
+    return _unpack_result(res)
+
+
 class PendingSearch:
     """A submitted search (kwage_search_submit); collect() waits for it and returns the result."""
 
@@ -308,6 +319,7 @@ def submit(group: Group, batch: Batch, threshold: float, flags: int = 0) -> Pend
 
 
 Group.search = lambda self, batch, threshold, flags=0: search(self, batch, threshold, flags)
+Group.search_topk = lambda self, batch, k, threshold=0.0, flags=0: search_topk(self, batch, k, threshold, flags)
 Group.submit = lambda self, batch, threshold, flags=0: submit(self, batch, threshold, flags)
 
 
@@ -435,6 +447,30 @@ class FileDatabase(Database):
         finally:
             b.close()
         out.sort(key=lambda h: (h.query, -h.num_kmers_found, h.path, h.column))
+        return out
+
+    def search_sequences_top(self, seqs: Sequence[bytes | str], k: int, threshold: float = 0.0) -> List[DatabaseHit]:
+        """What `kwage_top -k <k> -t <threshold> -d ... <seqs>` reports, as records: per query the k best samples of the
+        whole database under (score descending, file order, column ascending), listed by query, then descending hits.
+        Each group's own top k is a superset of its share of the database's top k, so the merge is exact."""
+        import bisect
+        order = {f: i for i, f in enumerate(self.files)}
+        b = Batch(self.ctx, seqs)
+        per_query = {}
+        try:
+            for g, layout in zip(self.groups, self._layout):
+                r = search_topk(g, b, k, threshold)
+                starts = [f[0] for f in layout]
+                for q, c, m in r.hits.tolist():
+                    i = bisect.bisect_right(starts, c) - 1
+                    first, _, path = layout[i]
+                    per_query.setdefault(q, []).append((m, path, c - first, int(r.num_query_kmer[q])))
+        finally:
+            b.close()
+        out: List[DatabaseHit] = []
+        for q in sorted(per_query):
+            best = sorted(per_query[q], key=lambda h: (-h[0], order[h[1]], h[2]))[:k]
+            out.extend(DatabaseHit(q, path, col, self._accession(path, col), m, nk) for m, path, col, nk in best)
         return out
 
     def close(self) -> None:

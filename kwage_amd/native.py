@@ -10,6 +10,8 @@ _CSRC = os.path.join(_HERE, "csrc")
 _LIB = os.path.join(_HERE, "lib", "libkwage_amd.so")
 KWAGE_BIN = os.path.join(_HERE, "bin", "kwage")
 KWAGE_DBTOOL_BIN = os.path.join(_HERE, "bin", "kwage_dbtool")
+KWAGE_TOP_BIN = os.path.join(_HERE, "bin", "kwage_top")
+TOPK_MAX = 1024              # KWAGE_TOPK_MAX
 
 
 class KwageError(RuntimeError):
@@ -42,7 +44,7 @@ def build_native(force: bool = False) -> str:
 def ensure_built() -> str:
     """Build the native library + CLI if (and only if) they are missing.  Used by bench.py / smoke();
     compiling the HIP extension is not a fallback -- nothing runs without it."""
-    if not (os.path.exists(_LIB) and os.path.exists(KWAGE_BIN) and os.path.exists(KWAGE_DBTOOL_BIN)):
+    if not all(os.path.exists(p) for p in (_LIB, KWAGE_BIN, KWAGE_TOP_BIN, KWAGE_DBTOOL_BIN)):
         build_native()
     return _LIB
 
@@ -131,6 +133,7 @@ _SIGNATURES = [
     ("kwage_batch_num_queries", C.c_uint32, [_P]),
     ("kwage_search", C.c_int, [_P, _P, C.c_float, C.c_uint32, C.POINTER(C.POINTER(Result))]),
     ("kwage_result_free", None, [C.POINTER(Result)]),
+    ("kwage_search_topk", C.c_int, [_P, _P, C.c_uint32, C.c_float, C.c_uint32, C.POINTER(C.POINTER(Result))]),
     ("kwage_search_submit", C.c_int, [_P, _P, C.c_float, C.c_uint32, C.POINTER(_P)]),
     ("kwage_search_collect", C.c_int, [_P, C.POINTER(C.POINTER(Result))]),
     ("kwage_search_poll", C.c_int, [_P]),
