@@ -249,6 +249,35 @@ void kwage_result_free(kwage_result *r);
 int kwage_search_topk(kwage_group *g, kwage_batch *b, uint32_t k, float threshold, uint32_t flags,
                       kwage_result **out);
 
+/* The top-k search with its records left on the device, for hosts that merge the lists of several groups, shards or
+ * passes themselves (kwage_node's top-k form): kwage_search_topk is to this what kwage_search is to
+ * kwage_search_device_append_submit.  The same records as kwage_search_topk selects, `column_base` added to every
+ * column, appended behind the *count_dev records already in hits_dev (count_dev: a device uint64, required;
+ * reset_count != 0 zeroes it first).  Records go query by query, each query's by column; records beyond `capacity` are
+ * counted, not stored (grow the buffer and redo the list).  num_query_kmer_dev may be NULL or a device buffer of
+ * n_queries uint32.  Synchronous, on the context's first stream: *n_total receives the running total, which is also
+ * in *count_dev when the call returns.  Timing flags are ignored.  Errors as kwage_search_topk, and KWAGE_ERR_ARG when
+ * column_base + the group's column span exceeds 32 bits. */
+int kwage_search_topk_device_append(kwage_group *g, kwage_batch *b, uint32_t k, float threshold, uint32_t flags,
+                                    void *hits_dev, uint64_t capacity, void *count_dev, uint32_t column_base,
+                                    int reset_count, void *num_query_kmer_dev, uint64_t *n_total);
+
+/* Device merge of top-k lists: hits_dev holds n_hits kwage_hit records (several lists concatenated, in any order).
+ * out_dev receives, per query, the first min(k, #records of the query) records under the key (num_match descending,
+ * order[column] ascending), ordered by (query, column) like every result; the output does not depend on the order of
+ * the input.  order_dev is a device array of n_order uint32 tie keys indexed by column (file order then column, for
+ * lists whose global columns are not in file order), or NULL: the tie key is the column itself.
+ * *out_count_dev (a device uint64, required) receives the output's record count.
+ * Preconditions, NOT checked: a (query, column) pair appears at most once; order is injective on the columns present.
+ * Errors (KWAGE_ERR_ARG): k = 0 or k > KWAGE_TOPK_MAX; a NULL ctx or out_count_dev, NULL hits_dev with n_hits > 0,
+ * NULL out_dev with out_capacity > 0; n_hits >= 2^32 or n_queries >= 2^31; records whose query is >= n_queries or,
+ * with an order table, whose column is >= n_order (found on the device, ignored by the merge, reported after it); an
+ * output larger than out_capacity (the first out_capacity records are written, *out_count_dev holds the full count).
+ * Synchronous; runs on the context's first stream; device scratch comes from the context's pool. */
+int kwage_topk_merge_device(kwage_ctx *ctx, const void *hits_dev, uint64_t n_hits, uint32_t n_queries, uint32_t k,
+                            const void *order_dev, uint64_t n_order, void *out_dev, uint64_t out_capacity,
+                            void *out_count_dev);
+
 /* The same search in two halves, for hosts that stream many batches: submit enqueues the whole device
  * pipeline and returns at once; collect waits for it and builds the result.  A context holds at most TWO
  * pending searches (each on its own HIP stream), so the k-mer stage, copy-back and host post-processing

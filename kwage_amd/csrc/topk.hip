@@ -21,6 +21,7 @@
 
 #include "kwage_amd.h"
 #include "engine_state.hpp"
+#include "pool_blocks.hpp"
 
 namespace topk_dev {
 #include "kernels.hpp"
@@ -82,25 +83,6 @@ int topk_layout(kwage_batch *b, uint32_t k, const KmerLayout **out)
 	b->layouts.push_back(std::move(L));
 	return KWAGE_OK;
 }
-
-// Device blocks of one call, taken from the context's batch pool and handed back when the call ends (after the stream
-// has been synchronised: nothing reads them any more).
-struct PoolBlocks {
-	DevPool *pool;
-	std::vector<DevPool::Block> held;
-	explicit PoolBlocks(DevPool *p) : pool(p) {}
-	~PoolBlocks() { for(const DevPool::Block &b : held){ pool->give(b.p, b.cap); } }
-	template <typename T>
-	int take(uint64_t bytes, T **out)
-	{
-		void *p = nullptr;
-		uint64_t cap = 0;
-		HIP_TRY(pool->take(bytes, &p, &cap));
-		held.push_back(DevPool::Block{p, cap});
-		*out = (T*)p;
-		return KWAGE_OK;
-	}
-};
 
 struct Events {
 	hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -202,14 +184,23 @@ struct TopkResultStorage {
 static const uint64_t CAND_BYTES_PER_SLICE = 256ull << 20;     // candidate keys of one slice of the batch's queries
 static const uint64_t SLAB_BYTES_PER_SLICE = 1ull << 30;       // partial counters of one slice (segmented form)
 
-int search_topk(kwage_group *g, kwage_batch *b, uint32_t k, float threshold, uint32_t flags, PoolBlocks &blocks, kwage_result **out)
+// What the selection stage leaves on the device: per query (batch order) the k-mer count, the floor and the number of
+// records selected, and up to k records per query in d_out[q*k ...], ordered by column (columns local to the group).
+struct TopkSelection {
+	uint32_t *d_nkmer = nullptr, *d_qthr = nullptr, *d_out_n = nullptr;
+	unsigned long long *d_missing = nullptr;      // sparse groups: row indices not among the group's rows
+	kwage_hit *d_out = nullptr;
+	uint32_t launches = 0;                        // 0: nothing was selected (no queries or no columns); d_out_n is unset
+	char kernel_name[64] = "";
+};
+
+// The selection stage of kwage_search_topk and kwage_search_topk_device_append: k-mer stage, tile kernels (or segments
+// + combine) and the per-query merge, queued on the context's first stream and not waited for.
+int topk_select(kwage_group *g, kwage_batch *b, uint32_t k, float threshold, uint32_t flags, PoolBlocks &blocks, Events &ev,
+                TopkSelection &sel)
 {
 	kwage_ctx *ctx = g->ctx;
 	int rc;
-	if(!g->finalized){ return fail(KWAGE_ERR_STATE, "kwage_group_finalize() must be called before searching"); }
-	if(b->ctx != ctx){ return fail(KWAGE_ERR_ARG, "batch and group belong to different contexts"); }
-	if(k < 1 || k > KWAGE_TOPK_MAX){ return fail(KWAGE_ERR_ARG, "kwage_search_topk: k must satisfy 1 <= k <= %u (got %u)", (unsigned)KWAGE_TOPK_MAX, k); }
-	if(!(threshold >= 0.0f && threshold <= 1.0f)){ return fail(KWAGE_ERR_ARG, "kwage_search_topk: threshold must satisfy 0 <= t <= 1"); }
 	if((rc = set_device(ctx))){ return rc; }
 	const KmerLayout *L = nullptr;
 	if((rc = topk_layout(b, g->params.kmer_len, &L))){ return rc; }
@@ -221,7 +212,6 @@ int search_topk(kwage_group *g, kwage_batch *b, uint32_t k, float threshold, uin
 	const uint32_t n = b->n;
 	const bool timing = (flags & KWAGE_SEARCH_TIMING) != 0;
 	const bool timing_kmer = timing && (flags & KWAGE_SEARCH_TIMING_KMER);
-	Events ev;
 	if(timing){ for(hipEvent_t &e : ev.ev){ HIP_TRY(hipEventCreate(&e)); } }
 
 	uint32_t *d_rows = nullptr, *d_nkmer = nullptr, *d_qthr = nullptr, *d_out_n = nullptr;
@@ -348,6 +338,42 @@ int search_topk(kwage_group *g, kwage_batch *b, uint32_t k, float threshold, uin
 		}
 	}
 	if(timing){ HIP_TRY(hipEventRecord(ev.ev[3], s)); }
+	sel.d_nkmer = d_nkmer;
+	sel.d_qthr = d_qthr;
+	sel.d_out_n = d_out_n;
+	sel.d_missing = d_missing;
+	sel.d_out = d_out;
+	sel.launches = launches;
+	memcpy(sel.kernel_name, kernel_name, sizeof(sel.kernel_name));
+	return KWAGE_OK;
+}
+
+int topk_check(kwage_group *g, kwage_batch *b, uint32_t k, float threshold, const char *what)
+{
+	if(!g->finalized){ return fail(KWAGE_ERR_STATE, "kwage_group_finalize() must be called before searching"); }
+	if(b->ctx != g->ctx){ return fail(KWAGE_ERR_ARG, "batch and group belong to different contexts"); }
+	if(k < 1 || k > KWAGE_TOPK_MAX){ return fail(KWAGE_ERR_ARG, "%s: k must satisfy 1 <= k <= %u (got %u)", what, (unsigned)KWAGE_TOPK_MAX, k); }
+	if(!(threshold >= 0.0f && threshold <= 1.0f)){ return fail(KWAGE_ERR_ARG, "%s: threshold must satisfy 0 <= t <= 1", what); }
+	return KWAGE_OK;
+}
+
+int search_topk(kwage_group *g, kwage_batch *b, uint32_t k, float threshold, uint32_t flags, PoolBlocks &blocks, kwage_result **out)
+{
+	int rc;
+	if((rc = topk_check(g, b, k, threshold, "kwage_search_topk"))){ return rc; }
+	Events ev;
+	TopkSelection sel;
+	if((rc = topk_select(g, b, k, threshold, flags, blocks, ev, sel))){ return rc; }
+	kwage_ctx *ctx = g->ctx;
+	hipStream_t s = ctx->stream;
+	const uint32_t n = b->n;
+	const uint32_t nh = g->params.num_hash;
+	const bool timing = (flags & KWAGE_SEARCH_TIMING) != 0;
+	const bool timing_kmer = timing && (flags & KWAGE_SEARCH_TIMING_KMER);
+	uint32_t *d_nkmer = sel.d_nkmer, *d_qthr = sel.d_qthr, *d_out_n = sel.d_out_n;
+	unsigned long long *d_missing = sel.d_missing;
+	kwage_hit *d_out = sel.d_out;
+	const uint32_t launches = sel.launches;
 
 	// ---- copy back: per-query arrays, missing-row counter, the <= k records per query -----------------------------------
 	std::unique_ptr<TopkResultStorage> rs(new (std::nothrow) TopkResultStorage());
@@ -394,9 +420,54 @@ int search_topk(kwage_group *g, kwage_batch *b, uint32_t k, float threshold, uin
 	if(timing_kmer){ HIP_TRY(hipEventElapsedTime(&r.kmer_kernel_ms, ev.ev[0], ev.ev[1])); }
 	if(timing){ HIP_TRY(hipEventElapsedTime(&r.search_kernel_ms, ev.ev[2], ev.ev[3])); }
 	r.search_kernel_launches = launches;
-	memcpy(rs->kernel, kernel_name, sizeof(rs->kernel));
+	memcpy(rs->kernel, sel.kernel_name, sizeof(rs->kernel));
 	r.search_kernel = rs->kernel;
 	*out = &rs.release()->pub;
+	return KWAGE_OK;
+}
+
+int search_topk_device_append(kwage_group *g, kwage_batch *b, uint32_t k, float threshold, uint32_t flags, void *hits_dev,
+                              uint64_t capacity, void *count_dev, uint32_t column_base, int reset_count,
+                              void *num_query_kmer_dev, PoolBlocks &blocks, uint64_t *n_total)
+{
+	int rc;
+	if((rc = topk_check(g, b, k, threshold, "kwage_search_topk_device_append"))){ return rc; }
+	if((uint64_t)column_base + g->stride*8 > 0x100000000ull){
+		return fail(KWAGE_ERR_ARG, "kwage_search_topk_device_append: column base %u + the group's column span exceeds 32 bits", column_base);
+	}
+	Events ev;
+	TopkSelection sel;
+	if((rc = topk_select(g, b, k, threshold, flags & ~(uint32_t)(KWAGE_SEARCH_TIMING | KWAGE_SEARCH_TIMING_KMER), blocks, ev, sel))){ return rc; }
+	hipStream_t s = g->ctx->stream;
+	const uint32_t n = b->n;
+	std::vector<uint32_t> out_n(n, 0);
+	unsigned long long missing = 0, base = 0;
+	if(sel.launches){ HIP_TRY(hipMemcpyAsync(out_n.data(), sel.d_out_n, (size_t)n*sizeof(uint32_t), hipMemcpyDeviceToHost, s)); }
+	HIP_TRY(hipMemcpyAsync(&missing, sel.d_missing, sizeof(missing), hipMemcpyDeviceToHost, s));
+	if(!reset_count){ HIP_TRY(hipMemcpyAsync(&base, count_dev, sizeof(base), hipMemcpyDeviceToHost, s)); }
+	HIP_TRY(hipStreamSynchronize(s));
+	if(missing){
+		return fail(KWAGE_ERR_STATE, "%llu row indices of this batch are not among the rows of the sparse group (it was created for other queries)", missing);
+	}
+	// the output offsets of the queries, in batch order: the list grows by query, then column, behind what it held
+	std::vector<unsigned long long> off(std::max<uint32_t>(n, 1), 0);
+	unsigned long long added = 0;
+	for(uint32_t q = 0; q < n; ++q){ off[q] = added; added += std::min(out_n[q], k); }
+	const unsigned long long total = base + added;
+	if(added){
+		unsigned long long *d_off = nullptr;
+		if((rc = blocks.take((uint64_t)n*sizeof(unsigned long long), &d_off))){ return rc; }
+		HIP_TRY(hipMemcpyAsync(d_off, off.data(), (size_t)n*sizeof(unsigned long long), hipMemcpyHostToDevice, s));
+		hipLaunchKernelGGL(dev::topk_append_kernel, dim3(n), dim3(dev::WAVE), 0, s, sel.d_out, sel.d_out_n, k, d_off, base,
+		                   column_base, (kwage_hit*)hits_dev, (unsigned long long)capacity);
+		HIP_TRY(hipGetLastError());
+	}
+	HIP_TRY(hipMemcpyAsync(count_dev, &total, sizeof(total), hipMemcpyHostToDevice, s));
+	if(num_query_kmer_dev && n){
+		HIP_TRY(hipMemcpyAsync(num_query_kmer_dev, sel.d_nkmer, (size_t)n*sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+	}
+	HIP_TRY(hipStreamSynchronize(s));
+	*n_total = total;
 	return KWAGE_OK;
 }
 
@@ -412,6 +483,23 @@ extern "C" int kwage_search_topk(kwage_group *g, kwage_batch *b, uint32_t k, flo
 	if(rc){
 		// an error return may leave kernels of this call queued: nothing of it may still run when `blocks` hands its
 		// device memory back to the pool (its destructor, below)
+		(void)hipStreamSynchronize(g->ctx->stream);
+		(void)hipGetLastError();
+	}
+	return rc;
+}
+
+extern "C" int kwage_search_topk_device_append(kwage_group *g, kwage_batch *b, uint32_t k, float threshold, uint32_t flags,
+                                               void *hits_dev, uint64_t capacity, void *count_dev, uint32_t column_base,
+                                               int reset_count, void *num_query_kmer_dev, uint64_t *n_total)
+{
+	if(!g || !b || !count_dev || !n_total || (capacity && !hits_dev)){
+		return kwage::fail(KWAGE_ERR_ARG, "kwage_search_topk_device_append: NULL argument");
+	}
+	kwage::PoolBlocks blocks(&g->ctx->batch_pool);
+	const int rc = kwage::search_topk_device_append(g, b, k, threshold, flags, hits_dev, capacity, count_dev, column_base,
+	                                                reset_count, num_query_kmer_dev, blocks, n_total);
+	if(rc){      // as kwage_search_topk: nothing of this call may still run when `blocks` hands its memory back
 		(void)hipStreamSynchronize(g->ctx->stream);
 		(void)hipGetLastError();
 	}

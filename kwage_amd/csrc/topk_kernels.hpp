@@ -10,6 +10,7 @@
 //                        (count_combine_kernel's tree) and selects the same way.
 //   topk_merge_kernel    one workgroup per query: radix select over the tiles' candidates, the <= k winners written
 //                        ordered by column.
+//   topk_append_kernel   kwage_search_topk_device_append: the selected records appended to the caller's device list.
 //
 // Candidates are 64-bit keys: score << 32 | (~column).  Keys of one query are distinct (columns are), and key order
 // descending is exactly the contract's (score descending, column ascending).
@@ -257,6 +258,24 @@ __global__ __launch_bounds__(MERGE_THREADS) void topk_merge_kernel(TopkArgs t, u
 		__syncthreads();
 	}
 	if(tid == 0){ out_n[q] = min(base, k); }
+}
+
+// kwage_search_topk_device_append's output stage: query q's <= k selected records (sel[q*k ...], ordered by column) go
+// to out[base + off[q] ...] with column_base added to the column; records at or beyond `capacity` are not written (the
+// host has counted them).  One workgroup per query.
+__global__ __launch_bounds__(WAVE) void topk_append_kernel(const kwage_hit *sel, const uint32_t *sel_n, uint32_t k,
+                                                          const unsigned long long *off, unsigned long long base,
+                                                          uint32_t column_base, kwage_hit *out, unsigned long long capacity)
+{
+	const uint32_t q = blockIdx.x;
+	const uint32_t m = min(sel_n[q], k);
+	const unsigned long long o = base + off[q];
+	for(uint32_t i = threadIdx.x; i < m; i += WAVE){
+		if(o + i >= capacity){ break; }
+		kwage_hit h = sel[(uint64_t)q*k + i];
+		h.column += column_base;
+		out[o + i] = h;
+	}
 }
 
 }  // namespace kwage

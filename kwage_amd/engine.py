@@ -295,6 +295,54 @@ def search_topk(group: Group, batch: Batch, k: int, threshold: float = 0.0, flag
     return _unpack_result(res)
 
 
+def _device_tensor(t, name: str, dtype, cols: int = 0):
+    import torch
+    if not isinstance(t, torch.Tensor) or t.device.type != "cuda" or t.dtype != dtype or not t.is_contiguous():
+        raise ValueError("%s: a contiguous %s tensor on a device is required" % (name, dtype))
+    if cols and (t.dim() != 2 or t.shape[1] != cols):
+        raise ValueError("%s: shape [n, %d] required, got %s" % (name, cols, tuple(t.shape)))
+    # the engine runs on its own stream: what torch queued for these tensors must be done first
+    torch.cuda.current_stream(t.device).synchronize()
+    return t
+
+
+def search_topk_device_append(group: Group, batch: Batch, k: int, hits, count, column_base: int = 0, threshold: float = 0.0,
+                              reset: bool = True, flags: int = 0, num_query_kmer=None) -> int:
+    """kwage_search_topk_device_append(): search_topk's records left on the device, `column_base` added to their columns,
+    appended to `hits` (int32 [capacity, 3] device tensor of (query, column, num_match) rows) behind the count[0]
+    records already there; `count` is an int64 [1] device tensor (zeroed first when `reset`).  Records beyond the
+    capacity are counted, not stored.  Returns the running total."""
+    import torch
+    _device_tensor(hits, "hits", torch.int32, 3)
+    _device_tensor(count, "count", torch.int64)
+    nk = 0 if num_query_kmer is None else _device_tensor(num_query_kmer, "num_query_kmer", torch.int32).data_ptr()
+    total = C.c_uint64()
+    check(lib().kwage_search_topk_device_append(group._h, batch._h, min(max(int(k), 0), 0xFFFFFFFF), C.c_float(threshold), flags,
+                                                hits.data_ptr() or None, hits.shape[0], count.data_ptr(), int(column_base),
+                                                1 if reset else 0, nk or None, C.byref(total)))
+    return int(total.value)
+
+
+def merge_topk_device(ctx: Context, hits, n_queries: int, k: int, order=None):
+    """kwage_topk_merge_device(): top-k lists concatenated in `hits` (int32 [n, 3] device tensor of (query, column,
+    num_match) rows, any order) merged to each query's first k records under (num_match descending, order[column]
+    ascending; the column itself without `order`, an int32 device tensor indexed by column).  Returns an int32
+    [m, 3] device tensor ordered by (query, column)."""
+    import torch
+    _device_tensor(hits, "hits", torch.int32, 3)
+    n = hits.shape[0]
+    cap = min(n, int(n_queries) * max(int(k), 0))
+    out = torch.empty((max(cap, 1), 3), dtype=torch.int32, device=hits.device)
+    count = torch.empty(1, dtype=torch.int64, device=hits.device)
+    optr, n_order = None, 0
+    if order is not None:
+        _device_tensor(order, "order", torch.int32)
+        optr, n_order = order.data_ptr() or None, order.numel()
+    check(lib().kwage_topk_merge_device(ctx._h, hits.data_ptr() if n else None, n, int(n_queries), min(max(int(k), 0), 0xFFFFFFFF),
+                                        optr, n_order, out.data_ptr(), cap, count.data_ptr()))
+    return out[:int(count.item())]
+
+
 class PendingSearch:
     """A submitted search (kwage_search_submit); collect() waits for it and returns the result."""
 
@@ -364,6 +412,35 @@ class Database:
     def search(self, batch: Batch, threshold: float, flags: int = 0) -> List[SearchResult]:
         # the k-mer stage is re-run per group: row indices depend on log_2_filter_len (kwage.cpp:411-412)
         return [search(g, batch, threshold, flags) for g in self.groups]
+
+    def search_topk(self, batch: Batch, k: int, threshold: float = 0.0) -> List[List[Tuple[int, int, int]]]:
+        """Per query, the k best columns of the whole database under (score descending, group order, column ascending):
+        every group's top-k list appended to one device list at its own column base (groups in order, so the global
+        column IS the tie order), merged on the device.  Returns per query [(group, column, num_match), ...] in
+        selection order."""
+        import torch
+        dev = torch.device("cuda", self.groups[0].ctx.device) if self.groups else None
+        bases, at = [], 0
+        for g in self.groups:
+            bases.append(at)
+            at += g.column_span
+        if at > 1 << 32:
+            raise OverflowError("Database.search_topk: %d columns do not fit the 32-bit column field" % at)
+        out: List[List[Tuple[int, int, int]]] = [[] for _ in range(batch.n)]
+        if not self.groups or not batch.n:
+            return out
+        hits = torch.empty((len(self.groups) * batch.n * min(max(int(k), 1), TOPK_MAX), 3), dtype=torch.int32, device=dev)
+        count = torch.empty(1, dtype=torch.int64, device=dev)
+        for gi, (g, base) in enumerate(zip(self.groups, bases)):
+            n = search_topk_device_append(g, batch, k, hits, count, base, threshold, reset=(gi == 0))
+        merged = merge_topk_device(self.groups[0].ctx, hits[:n], batch.n, k).cpu().numpy().view(np.uint32)
+        import bisect
+        for q, c, m in merged.tolist():
+            gi = bisect.bisect_right(bases, c) - 1
+            out[q].append((gi, c - bases[gi], m))
+        for lst in out:
+            lst.sort(key=lambda h: (-h[2], h[0], h[1]))
+        return out
 
     def close(self) -> None:
         for g in self.groups:

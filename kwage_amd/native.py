@@ -11,6 +11,7 @@ _LIB = os.path.join(_HERE, "lib", "libkwage_amd.so")
 KWAGE_BIN = os.path.join(_HERE, "bin", "kwage")
 KWAGE_DBTOOL_BIN = os.path.join(_HERE, "bin", "kwage_dbtool")
 KWAGE_TOP_BIN = os.path.join(_HERE, "bin", "kwage_top")
+KWAGE_TOP_NODE_BIN = os.path.join(_HERE, "bin", "kwage_top_node")
 TOPK_MAX = 1024              # KWAGE_TOPK_MAX
 
 
@@ -134,6 +135,8 @@ _SIGNATURES = [
     ("kwage_search", C.c_int, [_P, _P, C.c_float, C.c_uint32, C.POINTER(C.POINTER(Result))]),
     ("kwage_result_free", None, [C.POINTER(Result)]),
     ("kwage_search_topk", C.c_int, [_P, _P, C.c_uint32, C.c_float, C.c_uint32, C.POINTER(C.POINTER(Result))]),
+    ("kwage_search_topk_device_append", C.c_int, [_P, _P, C.c_uint32, C.c_float, C.c_uint32, _P, C.c_uint64, _P, C.c_uint32, C.c_int, _P, C.POINTER(C.c_uint64)]),
+    ("kwage_topk_merge_device", C.c_int, [_P, _P, C.c_uint64, C.c_uint32, C.c_uint32, _P, C.c_uint64, _P, C.c_uint64, _P]),
     ("kwage_search_submit", C.c_int, [_P, _P, C.c_float, C.c_uint32, C.POINTER(_P)]),
     ("kwage_search_collect", C.c_int, [_P, C.POINTER(C.POINTER(Result))]),
     ("kwage_search_poll", C.c_int, [_P]),
