@@ -2,8 +2,8 @@
 """bench.py -- throughput of the kwage search path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c3|c4|c5|c5s|c2t|c1]
-                    [--scaling weak|strong] [--also auto|none|c3,c4,...] [--share-of K [--share-rank R]]
-                    [--dump-outputs DIR]
+                    [--scaling weak|strong] [--share-of K [--share-rank R]] [--dump-outputs DIR]
+                    [--full [--also auto|none|c3,c4,...] [--no-sustained] [--no-result-check] ...]
 
 A "step" is one pass of the hot path over one batch of synthetic queries against the
 HBM-resident synthetic database (k-mer pack + MurmurHash3 + row gather + AND/count + hit
@@ -11,10 +11,19 @@ compaction + D2H of the sorted hit list).  Inputs (database and query strings) a
 HBM before the timed region.  Metric = BASELINE.json's: G k-mer.sample bit-tests/s, with the
 achieved HBM GB/s of the gather kernel against the 8 TB/s roofline beside it.
 
-The line the driver reads (ONE JSON line, the last of stdout) is the headline workload -- C2, the configuration
-BASELINE.json quotes the metric on, unchanged from round to round -- and carries, beside `roofline`, `sustained`,
-`aggregate` and `cpu_baseline`:
+The result is ONE JSON line, the last of stdout: the headline workload -- C2, the configuration BASELINE.json quotes
+the metric on, unchanged from round to round -- with `ms_per_step`, `roofline` (from the timed kernel's own times) and
+`aggregate`.  A plain run does only what that line needs: it builds the workload, warms up, times the steps, writes
+--dump-outputs if asked, prints the line and exits.
 
+--full adds everything else the benchmark measures or checks, never inside the timed region: `sustained` (the same
+steps back to back for 2 s after the timed ones), the HBM stream probe behind `roofline.measured_stream_read_gbps` /
+`frac_of_measured_stream` and `config.box.measured_stream_read_gbps`, `cpu_baseline` (below) and the blocks listed
+here.  The --no-* switches leave single blocks out of a --full run.
+
+  * `exchange_check` (N > 1, untimed, after the warm-up): every rank's hit count and an order-independent checksum of
+    its records against what rank 0 holds after the exchange; a mismatch ends the run with a non-zero status on every
+    rank.
   * `result_check`: AFTER the timed region the hit lists the timed kernel produced are checked -- every query cut from
     a planted genome reports the genome's columns, and three sampled queries are bit-exact against the CPU oracle on the
     rows they address, read back from HBM.  The oracle is used here as the checker only, never inside a timed region;
@@ -25,11 +34,11 @@ BASELINE.json quotes the metric on, unchanged from round to round -- and carries
     read), `fetched_bytes` from the PMC pass of `bench.py --workload X --early-exit` (profiles/pmc_traffic.json "X@ee")
     with `frac_of_fetched` = fetched bytes / kernel time / 8 TB/s, `identical_to_nominal` (the hit lists equal the timed
     kernel's record for record) and its own `result_check`.  Never part of `value`.
-  * `also`: the other BASELINE.json configurations this launch can hold, each measured like the headline (own
-    `ms_per_step`, `roofline`, `early_exit`, `result_check`, at N > 1 `exchange_check`) after the headline's matrix was
-    freed: at N = 1 **C3** (the largest 1-GPU configuration), at N > 1 the per-GPU shares of **C4** and **C5** and
-    **`c3_strong`** -- C3's 1 M columns SPLIT over the N ranks: the fixed-total-work curve (its N = 1 point is the
-    N = 1 line's `also.c3`), next to the weak-scaling headline.
+  * `also` (chosen by --also): the other BASELINE.json configurations this launch can hold, each measured like the
+    headline (own `ms_per_step`, `roofline`, `early_exit`, `result_check`, at N > 1 `exchange_check`) after the
+    headline's matrix was freed: at N = 1 **C3** (the largest 1-GPU configuration), at N > 1 the per-GPU shares of
+    **C4** and **C5** and **`c3_strong`** -- C3's 1 M columns SPLIT over the N ranks: the fixed-total-work curve (its
+    N = 1 point is the N = 1 line's `also.c3`), next to the weak-scaling headline.
 
 N > 1: one process per GPU.  Either the caller starts the ranks (`python -m torch.distributed.run
 --nproc-per-node N ... bench.py --gpus N`: RANK / LOCAL_RANK / WORLD_SIZE come from the environment), or
@@ -87,8 +96,10 @@ def parse_args(argv=None):
                     help="weak: every rank holds the workload's columns; strong: the workload's columns are split over the ranks")
     ap.add_argument("--share-of", type=int, default=0, help="one GPU holding one rank's share of a K-way strong split (the strong-scaling proxy)")
     ap.add_argument("--share-rank", type=int, default=0, help="which rank's share --share-of holds")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need (the blocks below, the CPU baseline and the other configurations); a plain run only sets up, warms up, times the steps and prints the line")
     ap.add_argument("--also", default=os.environ.get("KWAGE_BENCH_ALSO", "auto"),
-                    help="other configurations measured after the headline: auto (N=1: c3; N>1: c4,c5 -- only when the headline is c2), none, or a comma list")
+                    help="other configurations a --full run measures after the headline: auto (N=1: c3; N>1: c4,c5 -- only when the headline is c2), none, or a comma list")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-baseline", choices=("auto", "sample"), default="auto",
                     help="auto: the reference on the IDENTICAL database (the resident matrix written as .db files) where the host has room, plus the bounded sample; sample: the bounded sample only")
@@ -646,16 +657,16 @@ class Env:
 
 
 def measure(env, args, name, headline, force_scaling=None):
-    """Build workload `name` on this rank, run warm-up + EXACTLY args.steps timed steps (+ the sustained block for the
-    headline), check the results, free everything.  -> the JSON block on rank 0, None elsewhere.  Raises SystemExit(3/4)
-    on every rank when the exchange or the results fail their check."""
+    """Build workload `name` on this rank, run warm-up + EXACTLY args.steps timed steps (with --full: + the sustained block
+    for the headline, the checks and the other blocks), free everything.  -> the JSON block on rank 0, None elsewhere.
+    Raises SystemExit(3/4) on every rank when the exchange or the results fail their check."""
     import numpy as np
     import torch
     import kwage_amd as ka
     from kwage_amd import synth
     rank, local_rank, world, backend, cdev, dist, ctx = env.rank, env.local_rank, env.world, env.backend, env.cdev, env.dist, env.ctx
     sharded, force_sharded = env.sharded, env.force_sharded
-    want_sustained = headline and not args.no_sustained
+    want_sustained = headline and args.full and not args.no_sustained
 
     split = args.share_of if args.share_of > 1 else world
     part = (args.share_rank if args.share_of > 1 else rank)
@@ -766,6 +777,7 @@ def measure(env, args, name, headline, force_scaling=None):
             merged = None
             for buf, n in pending:
                 merged = hx.exchange_step(buf, n)
+        if pipe is not None and args.full:
             # ---- untimed self-check of the exchange: what rank 0 holds after the gather is exactly what the ranks
             # found -- every rank's record count and an order-independent checksum of its (query, global column,
             # num_match) records against the merged list.
@@ -896,7 +908,7 @@ def measure(env, args, name, headline, force_scaling=None):
 
     # ---- result_check: the lists the timed kernel produced (rank-local, before any exchange) ------------------------
     rcheck = None
-    if not args.no_result_check:
+    if args.full and not args.no_result_check:
         try:
             rcheck = result_check(members, probe, threshold)
         except Exception as exc:          # a checker that cannot run is a failed check, not a skipped one
@@ -904,7 +916,7 @@ def measure(env, args, name, headline, force_scaling=None):
     # ---- early_exit: the SAME batch against the SAME resident matrix with the reference's early exit (kwage.cpp:437-483)
     # on -- what `kwage` and `kwage_node` run by default.  After the timed region (never part of `value`); rank-local.
     ee = None
-    if not args.no_early_exit_block and not args.early_exit:
+    if args.full and not args.no_early_exit_block and not args.early_exit:
         try:
             ee = early_exit_block(args, name, members, s, threshold, flags, probe, pmc_applies=not (scaling == "strong" and split > 1))
         except Exception as exc:
@@ -936,7 +948,12 @@ def measure(env, args, name, headline, force_scaling=None):
         value = bit_tests_all * args.steps / dt / 1e9
         k_ms = per_rank[0][0]
         achieved = alg_bytes_rank / (k_ms * 1e-3) / 1e9 if k_ms > 0 else 0.0
-        stream_gbps = s.group.stream_read_gbps(min(s.group.device_bytes, 8 << 30), 3)
+        # the box's streaming-read rate beside the kernel's: a run of its own, so --full only
+        stream_box, stream_roofline = {}, {}
+        if args.full:
+            stream_gbps = s.group.stream_read_gbps(min(s.group.device_bytes, 8 << 30), 3)
+            stream_box = {"measured_stream_read_gbps": round(stream_gbps, 1)}
+            stream_roofline = dict(stream_box, frac_of_measured_stream=round(achieved / stream_gbps, 4) if stream_gbps else None)
         kernel = getattr(probe, "search_kernel", "") or ("and_kernel" if threshold == 1.0 else "count_kernel")
         traffic, traffic_source = (None, {"status": "no PMC pass for a %d-way share" % split}) if scaling == "strong" and split > 1 \
             else measured_traffic(name, kernel, args.early_exit)
@@ -966,7 +983,7 @@ def measure(env, args, name, headline, force_scaling=None):
                        "total_kmers_per_step": int(probe.total_kmers) if not multi else None, "hits_per_step": int(nhits),
                        "db_build_s": round(t_build, 2),
                        # which box this is (kwage_device_fingerprint) and what its HBM streams: boxes of the pool differ by several per cent
-                       "box": dict(ctx.fingerprint(), measured_stream_read_gbps=round(stream_gbps, 1), host=socket.gethostname()),
+                       "box": dict(ctx.fingerprint(), **stream_box, host=socket.gethostname()),
                        # how the loader chose each matrix's device block (rank 0): candidates compared, gather-probe GB/s on the kept / released one
                        "matrix_placement": [m.group.placement for m in multi] if multi else s.group.placement,
                        "seeds": {"queries_and_planted_genomes": 1, "columns": "rank (splitmix64 keyed by seed, row, word; kwage_amd/synth.py)"}},
@@ -978,9 +995,7 @@ def measure(env, args, name, headline, force_scaling=None):
                          # HIP events on the search's stream around the gather STAGE: one launch, except for and_band_walk_kernel,
                          # whose bucketing launch and finish launch are inside (rocprofv3's average for that kernel alone is ~2 % less)
                          "kernel_ms_scope": "gather stage" + (" = bucketing launch + and_band_walk_kernel + finish launch" if kernel.startswith("and_band_walk") else " = one launch"),
-                         "algorithmic_bytes_per_launch": alg_bytes_rank,
-                         "measured_stream_read_gbps": round(stream_gbps, 1),
-                         "frac_of_measured_stream": round(achieved / stream_gbps, 4) if stream_gbps else None},
+                         "algorithmic_bytes_per_launch": alg_bytes_rank, **stream_roofline},
             # all ranks: every GPU's algorithmic bytes over the SLOWEST rank's mean kernel time, against N x 8 TB/s
             "aggregate": {"n_gpus": world, "kernel_ms_per_rank": [round(x, 4) for x in k_means],
                           "kernel_ms_max": round(k_max, 4), "kernel_ms_mean": round(k_mean, 4),
@@ -1019,7 +1034,7 @@ def measure(env, args, name, headline, force_scaling=None):
             out["dump_outputs"] = write_outputs(args.dump_outputs, dumped)
         if force_sharded:
             out["config"]["note"] = "KWAGE_BENCH_FORCE_SHARDED: multi-GPU code path on one rank"
-        if headline and world == 1 and not args.no_cpu_baseline:
+        if headline and world == 1 and args.full and not args.no_cpu_baseline:
             # the planned baseline first -- the reference on the IDENTICAL database, whole-list parity included --, where the
             # host has the room (105 GB of files for C2) and the reference binary travelled; the bounded sample always (it is
             # the one that reads every addressed row, like `value`)
@@ -1111,7 +1126,7 @@ def rank_main(args):
     out = measure(env, args, args.workload, True)
 
     # ---- the other BASELINE.json configurations this launch can hold, after the headline's matrix was freed ------------
-    names = also_workloads(args, world)
+    names = also_workloads(args, world) if args.full else []
     if names:
         if rank == 0:     # a copy of the headline on stderr first: whatever happens below, the number is on record
             print("[bench] headline (the `also` blocks follow): " + json.dumps(out), file=sys.stderr, flush=True)

@@ -111,7 +111,7 @@ def test_bench_self_launches_two_ranks_on_one_gpu():
     aggregate block, every rank's kernel time, and twice the single-rank work."""
     env = dict(os.environ, KWAGE_BENCH_BACKEND="gloo", KWAGE_BENCH_ONE_DEVICE="1")
     env.pop("WORLD_SIZE", None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--workload", "tiny"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--workload", "tiny", "--full"],
                        capture_output=True, text=True, env=env, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
@@ -127,7 +127,7 @@ def test_bench_self_launches_two_ranks_on_one_gpu():
     assert ec["ok"] and ec["ranks"] == 2 and ec["hits"] == sum(ec["hits_per_rank"]) and ec["checksum"] == ec["sum_of_rank_checksums"]
     assert ec["sorted_unique"] and ec["columns_in_range"] and line["config"]["hits_per_step"] == ec["hits"]
     assert line["rccl"]["searches_per_step"] == 1
-    one = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "1", "--workload", "tiny", "--no-cpu-baseline", "--no-sustained"],
+    one = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "1", "--workload", "tiny", "--full", "--no-cpu-baseline", "--no-sustained"],
                          capture_output=True, text=True, env=env, timeout=900)
     assert one.returncode == 0, one.stderr[-3000:]
     single = json.loads(one.stdout.strip().splitlines()[-1])
@@ -135,7 +135,7 @@ def test_bench_self_launches_two_ranks_on_one_gpu():
     assert line["roofline"]["algorithmic_bytes_per_launch"] == single["roofline"]["algorithmic_bytes_per_launch"]    # weak scaling: same share per GPU
     # the C5 code path (several filter-size groups per rank: ONE list and ONE exchange per step for all of them, the
     # searches pipelined through the context's two slots) on toy groups, two ranks
-    r5 = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--workload", "c5tiny", "--no-sustained"],
+    r5 = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--workload", "c5tiny", "--full", "--no-sustained"],
                         capture_output=True, text=True, env=env, timeout=900)
     assert r5.returncode == 0, r5.stderr[-3000:]
     l5 = json.loads(r5.stdout.strip().splitlines()[-1])
@@ -155,14 +155,14 @@ def test_bench_self_launches_two_ranks_on_one_gpu():
     # `also` blocks at N > 1 (the driver's 8-GPU run measures the C4 and C5 shares behind the C2 headline): the same code on
     # toy workloads -- every block with its own exchange_check and result_check -- and strong scaling (the columns of the
     # workload split over the ranks at 1024-column boundaries: the ranks' algorithmic bytes differ and add up)
-    ra = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--workload", "tiny", "--no-sustained",
+    ra = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--workload", "tiny", "--full", "--no-sustained",
                          "--also", "c5tiny"], capture_output=True, text=True, env=env, timeout=900)
     assert ra.returncode == 0, ra.stderr[-3000:]
     la = json.loads(ra.stdout.strip().splitlines()[-1])
     blk = la["also"]["c5tiny"]
     assert la["scaling"] == "weak" and la["config"]["total_samples"] == 10000 and la["exchange_check"]["ok"] and la["result_check"]["ok"]
     assert blk["exchange_check"]["ok"] and blk["result_check"]["ok"] and blk["roofline"]["kernel"].startswith("count_") and blk["rccl"]["searches_per_step"] == 4
-    rs = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--workload", "tiny", "--no-sustained",
+    rs = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--workload", "tiny", "--full", "--no-sustained",
                          "--scaling", "strong"], capture_output=True, text=True, env=env, timeout=900)
     assert rs.returncode == 0, rs.stderr[-3000:]
     ls = json.loads(rs.stdout.strip().splitlines()[-1])
@@ -265,6 +265,15 @@ def test_steps_and_warmup_are_validated():
             bench.parse_args(argv)
 
 
+def test_a_plain_run_leaves_the_other_blocks_to_full():
+    """Everything beyond the headline (sustained block, checks, early exit, CPU baseline, other configurations) runs
+    only with --full; the --no-* switches and --also keep their meaning inside a --full run."""
+    import bench
+    assert bench.parse_args([]).full is False
+    a = bench.parse_args(["--full", "--no-sustained", "--also", "c3_strong"])
+    assert a.full and a.no_sustained and bench.also_workloads(a, 2) == ["c3_strong"]
+
+
 def test_dump_outputs_writes_float64_arrays_within_the_budget(tmp_path):
     """step_outputs + write_outputs: a step's SearchResults become float64 .npy files; over the budget every hit list
     keeps the same seeded rows (row numbers beside them), the per-query arrays stay whole."""
@@ -303,20 +312,27 @@ def test_dump_outputs_writes_float64_arrays_within_the_budget(tmp_path):
 @pytest.mark.gpu
 def test_bench_dumps_what_its_last_timed_step_returned(tmp_path):
     """--dump-outputs on the GPU: the files hold exactly what one search of the same seeded batch returns, the same from
-    run to run, and --steps is the number of timed steps the line reports."""
+    run to run and with or without --full, and --steps is the number of timed steps the line reports.  A plain run's
+    line carries nothing that --full adds."""
     import numpy as np
     import kwage_amd as ka
     from kwage_amd import synth
     lines = []
-    for d in ("one", "two"):
-        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--workload", "tiny", "--no-cpu-baseline",
-                            "--no-sustained", "--no-early-exit-block", "--also", "none", "--dump-outputs", str(tmp_path / d)],
-                           capture_output=True, text=True, timeout=900)
+    for d, extra in (("one", ["--full", "--no-cpu-baseline", "--no-sustained", "--no-early-exit-block", "--also", "none"]), ("two", [])):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--workload", "tiny"] + extra
+                           + ["--dump-outputs", str(tmp_path / d)], capture_output=True, text=True, timeout=900)
         assert r.returncode == 0, r.stderr[-3000:]
         lines.append(json.loads(r.stdout.strip().splitlines()[-1]))
     line = lines[0]
     assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["result_check"]["ok"]
     assert line["dump_outputs"]["sampled"] == {} and line["dump_outputs"]["files"]["hits"] == [line["config"]["hits_per_step"], 3]
+    plain = lines[1]
+    assert all(plain[k] == line[k] for k in ("metric", "unit", "higher_is_better", "dtype"))
+    assert plain["steps"] == 3 and plain["warmup"] == 1 and plain["value"] > 0 and plain["ms_per_step"] > 0
+    assert plain["dump_outputs"]["files"] == line["dump_outputs"]["files"]
+    assert not {"sustained", "result_check", "early_exit", "cpu_baseline", "also", "exchange_check"} & set(plain)
+    assert "measured_stream_read_gbps" not in plain["roofline"] and "measured_stream_read_gbps" not in plain["config"]["box"]
+    assert "measured_stream_read_gbps" in line["roofline"] and "frac_of_measured_stream" in line["roofline"]
     names = sorted(p.name for p in (tmp_path / "one").iterdir())
     assert names == ["hits.npy", "num_query_kmer.npy", "query_threshold.npy"]
     for name in names:

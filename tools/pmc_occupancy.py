@@ -40,7 +40,7 @@ def main():
         shutil.rmtree(d, ignore_errors=True)
         os.makedirs(d)
         cmd = ["rocprofv3", "--pmc"] + COUNTERS + ["--output-format", "csv", "-d", d, "--",
-               sys.executable, os.path.join(ROOT, "bench.py"), "--workload", wl, "--no-cpu-baseline", "--no-sustained", "--no-result-check", "--also", "none", "--steps", "5", "--warmup", "1"]
+               sys.executable, os.path.join(ROOT, "bench.py"), "--workload", wl, "--full", "--no-cpu-baseline", "--no-sustained", "--no-result-check", "--also", "none", "--steps", "5", "--warmup", "1"]
         t0 = time.time()
         r = subprocess.run(cmd, capture_output=True, text=True, cwd="/tmp", env=dict(os.environ, TMPDIR="/tmp"))
         print("[pmc_occupancy] %s: rc %d in %.0f s" % (wl, r.returncode, time.time() - t0), flush=True)

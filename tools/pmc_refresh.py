@@ -51,7 +51,7 @@ def main():
         d = os.path.join(out_root, spec.replace("+", "_"))
         os.makedirs(d, exist_ok=True)
         cmd = ["rocprofv3", "--pmc", "FETCH_SIZE", "--output-format", "csv", "-d", d, "--",
-               sys.executable, os.path.join(ROOT, "bench.py"), "--workload", wl, "--no-cpu-baseline", "--no-sustained", "--no-result-check", "--no-early-exit-block", "--also", "none", "--steps", "5", "--warmup", "1"] + (["--early-exit"] if ee else [])
+               sys.executable, os.path.join(ROOT, "bench.py"), "--workload", wl, "--full", "--no-cpu-baseline", "--no-sustained", "--no-result-check", "--no-early-exit-block", "--also", "none", "--steps", "5", "--warmup", "1"] + (["--early-exit"] if ee else [])
         t0 = time.time()
         r = subprocess.run(cmd, capture_output=True, text=True, cwd="/tmp", env=dict(os.environ, TMPDIR="/tmp", **knobs))
         print("[pmc_refresh] %s: rc %d in %.0f s" % (wl, r.returncode, time.time() - t0), flush=True)

@@ -7,15 +7,15 @@ O=$R/gpurun_out/r04; mkdir -p $O
 cd $R
 case "$1" in
 lines)
-  python bench.py --steps 20 --warmup 5 > $O/r04_c2_bench.json 2> $O/r04_c2_bench.err
-  for w in c2t c4 c5s c5; do python bench.py --workload $w --no-cpu-baseline --steps 10 --warmup 3 > $O/r04_${w}_bench.json 2>/dev/null; done
-  python bench.py --workload c3 --no-cpu-baseline --steps 10 --warmup 3 > $O/r04_c3_bench.json 2>/dev/null
+  python bench.py --full --steps 20 --warmup 5 > $O/r04_c2_bench.json 2> $O/r04_c2_bench.err
+  for w in c2t c4 c5s c5; do python bench.py --full --workload $w --no-cpu-baseline --steps 10 --warmup 3 > $O/r04_${w}_bench.json 2>/dev/null; done
+  python bench.py --full --workload c3 --no-cpu-baseline --steps 10 --warmup 3 > $O/r04_c3_bench.json 2>/dev/null
   ;;
 rocprof)
   cd /tmp; export TMPDIR=/tmp
   for w in c2 c2t c4 c5; do
     rm -rf $O/prof_$w
-    rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$w -- python3 $R/bench.py --workload $w --no-cpu-baseline --steps 20 --warmup 5 > $O/r04_${w}_bench_under_rocprof.json 2>/dev/null
+    rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$w -- python3 $R/bench.py --full --workload $w --no-cpu-baseline --steps 20 --warmup 5 > $O/r04_${w}_bench_under_rocprof.json 2>/dev/null
     cp $(ls $O/prof_$w/*/*kernel_stats.csv | tail -1) $O/r04_${w}_kernel_stats.csv
     rm -rf $O/prof_$w
   done
@@ -25,9 +25,9 @@ pmc)
   cp gpurun_out/pmc_r04/pmc_traffic.json gpurun_out/pmc_r04/r04_*_pmc_fetch_size.json $O/
   ;;
 sharded)
-  for w in c2 c3 c5; do KWAGE_BENCH_FORCE_SHARDED=1 python bench.py --workload $w --no-cpu-baseline --also none --steps 10 --warmup 3 > $O/r04_${w}_bench_sharded_world1.json 2>/dev/null; done
-  KWAGE_BENCH_BACKEND=gloo KWAGE_BENCH_ONE_DEVICE=1 python bench.py --gpus 2 --also none --steps 10 --warmup 3 > $O/r04_c2_bench_two_ranks_one_gpu_gloo.json 2>/dev/null
-  KWAGE_BENCH_BACKEND=gloo KWAGE_BENCH_ONE_DEVICE=1 python bench.py --gpus 2 --scaling strong --also none --steps 10 --warmup 3 > $O/r04_c2_bench_two_ranks_one_gpu_gloo_strong.json 2>/dev/null
+  for w in c2 c3 c5; do KWAGE_BENCH_FORCE_SHARDED=1 python bench.py --full --workload $w --no-cpu-baseline --also none --steps 10 --warmup 3 > $O/r04_${w}_bench_sharded_world1.json 2>/dev/null; done
+  KWAGE_BENCH_BACKEND=gloo KWAGE_BENCH_ONE_DEVICE=1 python bench.py --full --gpus 2 --also none --steps 10 --warmup 3 > $O/r04_c2_bench_two_ranks_one_gpu_gloo.json 2>/dev/null
+  KWAGE_BENCH_BACKEND=gloo KWAGE_BENCH_ONE_DEVICE=1 python bench.py --full --gpus 2 --scaling strong --also none --steps 10 --warmup 3 > $O/r04_c2_bench_two_ranks_one_gpu_gloo_strong.json 2>/dev/null
   ;;
 proxy)
   python tools/strong_scaling_proxy.py --round r04 > $O/proxy.txt 2>&1

@@ -35,7 +35,7 @@ ee_stats)
   ;;
 count_ab)
   for w in c2t c5s; do for r in 0 1; do
-    KWAGE_EE_REFINE=$r python bench.py --workload $w --early-exit --no-cpu-baseline --no-sustained --also none --steps 10 --warmup 3 2>/dev/null | python -c "
+    KWAGE_EE_REFINE=$r python bench.py --full --workload $w --early-exit --no-cpu-baseline --no-sustained --also none --steps 10 --warmup 3 2>/dev/null | python -c "
 import json,sys
 l=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$w ee_refine=$r', l['ms_per_step'], l['roofline']['kernel'], l['roofline']['kernel_ms'], l['config']['hits_per_step'], l['result_check']['ok'])"
   done; done
@@ -53,27 +53,27 @@ identical)
 long1t)
   python -m pytest tests/test_gpu_parity.py tests/test_gpu_node_cli.py tests/test_gpu_random_configs.py -m gpu -x -q -k "2_pow_20 or long_quer or segments or node_cli or random_config or walk_rows_many" > $O/long_tests.txt 2>&1 || { tail -40 $O/long_tests.txt; exit 1; }
   tail -3 $O/long_tests.txt
-  python bench.py --workload long1t --no-cpu-baseline --also none --no-early-exit-block --steps 10 --warmup 3 2>/dev/null > $O/r05_long1t_bench.json
+  python bench.py --full --workload long1t --no-cpu-baseline --also none --no-early-exit-block --steps 10 --warmup 3 2>/dev/null > $O/r05_long1t_bench.json
   python -c "
 import json; l=json.loads(open('$O/r05_long1t_bench.json').read().strip().splitlines()[-1]); print('long1t', l['roofline']['kernel'], l['roofline']['kernel_ms'], l['roofline']['frac'], l['roofline']['frac_of_measured_stream'])"
   python tools/bench_long_query.py 2>&1 | tee $O/r05_long_query_segments.txt
   ;;
 lines)
-  python bench.py --steps 20 --warmup 5 > $O/r05_c2_bench.json 2> $O/r05_c2_bench.err
-  for w in c2t c4 c5s c5 c3 c2q5kt c2q100kt; do python bench.py --workload $w --no-cpu-baseline --steps 10 --warmup 3 > $O/r05_${w}_bench.json 2>/dev/null; echo "line $w done"; done
-  for w in c2 c2t c2q5k c3; do python bench.py --workload $w --early-exit --no-cpu-baseline --also none --steps 100 --warmup 5 > $O/r05_ee_${w}_bench.json 2>/dev/null; echo "ee line $w done"; done
+  python bench.py --full --steps 20 --warmup 5 > $O/r05_c2_bench.json 2> $O/r05_c2_bench.err
+  for w in c2t c4 c5s c5 c3 c2q5kt c2q100kt; do python bench.py --full --workload $w --no-cpu-baseline --steps 10 --warmup 3 > $O/r05_${w}_bench.json 2>/dev/null; echo "line $w done"; done
+  for w in c2 c2t c2q5k c3; do python bench.py --full --workload $w --early-exit --no-cpu-baseline --also none --steps 100 --warmup 5 > $O/r05_ee_${w}_bench.json 2>/dev/null; echo "ee line $w done"; done
   ;;
 rocprof)
   cd /tmp; export TMPDIR=/tmp
   for w in c2 c2t c4 c5; do
     rm -rf $O/prof_$w
-    rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$w -- python3 $R/bench.py --workload $w --no-cpu-baseline --steps 20 --warmup 5 > $O/r05_${w}_bench_under_rocprof.json 2>/dev/null
+    rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$w -- python3 $R/bench.py --full --workload $w --no-cpu-baseline --steps 20 --warmup 5 > $O/r05_${w}_bench_under_rocprof.json 2>/dev/null
     cp $(ls $O/prof_$w/*/*kernel_stats.csv | tail -1) $O/r05_${w}_kernel_stats.csv
     rm -rf $O/prof_$w; echo "rocprof $w done"
   done
   for w in c2 c2t c2q5k c3; do
     rm -rf $O/prof_ee_$w
-    rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_ee_$w -- python3 $R/bench.py --workload $w --early-exit --no-cpu-baseline --also none --steps 20 --warmup 5 > $O/r05_ee_${w}_bench_under_rocprof.json 2>/dev/null
+    rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_ee_$w -- python3 $R/bench.py --full --workload $w --early-exit --no-cpu-baseline --also none --steps 20 --warmup 5 > $O/r05_ee_${w}_bench_under_rocprof.json 2>/dev/null
     cp $(ls $O/prof_ee_$w/*/*kernel_stats.csv | tail -1) $O/r05_ee_${w}_kernel_stats.csv
     rm -rf $O/prof_ee_$w; echo "rocprof ee $w done"
   done
@@ -90,8 +90,8 @@ occupancy)
   tail -12 $O/pmc_occupancy.txt
   ;;
 sharded)
-  for w in c2 c3 c5; do KWAGE_BENCH_FORCE_SHARDED=1 python bench.py --workload $w --no-cpu-baseline --also none --steps 10 --warmup 3 > $O/r05_${w}_bench_sharded_world1.json 2>/dev/null; echo "sharded $w done"; done
-  KWAGE_BENCH_BACKEND=gloo KWAGE_BENCH_ONE_DEVICE=1 python bench.py --gpus 2 --also c3_strong --no-cpu-baseline --steps 10 --warmup 3 > $O/r05_c2_bench_two_ranks_one_gpu_gloo_also_c3_strong.json 2>$O/two_ranks.err || tail -20 $O/two_ranks.err
+  for w in c2 c3 c5; do KWAGE_BENCH_FORCE_SHARDED=1 python bench.py --full --workload $w --no-cpu-baseline --also none --steps 10 --warmup 3 > $O/r05_${w}_bench_sharded_world1.json 2>/dev/null; echo "sharded $w done"; done
+  KWAGE_BENCH_BACKEND=gloo KWAGE_BENCH_ONE_DEVICE=1 python bench.py --full --gpus 2 --also c3_strong --no-cpu-baseline --steps 10 --warmup 3 > $O/r05_c2_bench_two_ranks_one_gpu_gloo_also_c3_strong.json 2>$O/two_ranks.err || tail -20 $O/two_ranks.err
   python - <<PY
 import json
 l = json.loads(open("$O/r05_c2_bench_two_ranks_one_gpu_gloo_also_c3_strong.json").read().strip().splitlines()[-1])
@@ -124,20 +124,20 @@ refine_knobs)
   ;;
 count_check)
   for ck in 8 16 32 64; do for w in c2t c5s; do
-    KWAGE_COUNT_SCREEN_CHECK=$ck python bench.py --workload $w --early-exit --no-cpu-baseline --no-sustained --also none --steps 30 --warmup 3 2>/dev/null | python -c "
+    KWAGE_COUNT_SCREEN_CHECK=$ck python bench.py --full --workload $w --early-exit --no-cpu-baseline --no-sustained --also none --steps 30 --warmup 3 2>/dev/null | python -c "
 import json,sys
 l=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$w check=$ck', l['ms_per_step'], l['roofline']['kernel'], l['roofline']['kernel_ms'], l['result_check']['ok'])"
   done; done
   for ck in 8 16 32; do echo "check=$ck"; KWAGE_COUNT_SCREEN_CHECK=$ck python tools/step_breakdown.py "100k x 150" 2>&1 | grep " ee " | grep "t=0.8"; done
   ;;
 walk_hint)
-  for k in 1 2 4 8; do python bench.py --workload c2 --share-of $k --no-cpu-baseline --no-sustained --also none --no-early-exit-block --no-result-check --steps 20 --warmup 3 2>/dev/null | python -c "
+  for k in 1 2 4 8; do python bench.py --full --workload c2 --share-of $k --no-cpu-baseline --no-sustained --also none --no-early-exit-block --no-result-check --steps 20 --warmup 3 2>/dev/null | python -c "
 import json,sys
 l=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('c2 of $k', l['roofline']['kernel'], l['roofline']['kernel_ms'], l['roofline']['frac'], l['roofline']['frac_of_measured_stream'])"
   done
   ;;
 two_ranks)
-  KWAGE_BENCH_BACKEND=gloo KWAGE_BENCH_ONE_DEVICE=1 python bench.py --gpus 2 --also c3_strong --no-cpu-baseline --steps 10 --warmup 3 > $O/r05_c2_bench_two_ranks_one_gpu_gloo_also_c3_strong.json 2>$O/two_ranks.err || tail -20 $O/two_ranks.err
+  KWAGE_BENCH_BACKEND=gloo KWAGE_BENCH_ONE_DEVICE=1 python bench.py --full --gpus 2 --also c3_strong --no-cpu-baseline --steps 10 --warmup 3 > $O/r05_c2_bench_two_ranks_one_gpu_gloo_also_c3_strong.json 2>$O/two_ranks.err || tail -20 $O/two_ranks.err
   ;;
 trunc_ab)
   for shape in "200 x 5 kb" "10 x 100 kb" "1 x 10 kb"; do for tr in 0 1; do echo "== KWAGE_COUNT_TRUNC=$tr"; KWAGE_COUNT_TRUNC=$tr python tools/step_breakdown.py "$shape" 2>&1 | grep -E "t=0.8 "; done; done > $O/r05_count_trunc_ab.txt 2>&1
@@ -148,7 +148,7 @@ c5_groups)
   cut -c1-300 $O/r05_c5_ee_groups.txt
   ;;
 line)
-  python bench.py --steps 20 --warmup 5 > $O/r05_c2_bench.json 2> $O/r05_c2_bench.err || { tail -30 $O/r05_c2_bench.err; exit 1; }
+  python bench.py --full --steps 20 --warmup 5 > $O/r05_c2_bench.json 2> $O/r05_c2_bench.err || { tail -30 $O/r05_c2_bench.err; exit 1; }
   python - <<PY
 import json
 l = json.loads(open("$O/r05_c2_bench.json").read().strip().splitlines()[-1])

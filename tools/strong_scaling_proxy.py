@@ -68,7 +68,7 @@ def main():
             d = os.path.join(out_root, "%s_of%d" % (wl, k))
             shutil.rmtree(d, ignore_errors=True)
             os.makedirs(d, exist_ok=True)
-            cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--workload", wl, "--share-of", str(k), "--also", "none",
+            cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--workload", wl, "--share-of", str(k), "--full", "--also", "none",
                    "--no-cpu-baseline", "--no-sustained", "--steps", str(steps), "--warmup", "3"]
             if rocprof:
                 cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "--"] + cmd
