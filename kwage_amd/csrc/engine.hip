@@ -42,44 +42,184 @@ static const TuningName TUNING_NAMES[] = {
 	{"ext_launch_events", &Tuning::ext_launch_events}, {"group_contiguous", &Tuning::group_contiguous}, {"group_placement_probe", &Tuning::group_placement_probe},
 };
 
-namespace {
+namespace kwage {
 
-// Lay the result block out for n queries and at least min_cap hit records. Growing the block keeps
-// its head (counters + per-query arrays) when keep_head is set (hit-buffer growth mid-search).
-int layout_result(Slot *sl, uint32_t n, uint64_t min_cap, bool keep_head)
+// ------------------------------------------------------------------------------------------
+// The kernels of the search that are not templates (kernels.hpp names each where it belongs): defined in this
+// translation unit, the only one that launches them, because kernels.hpp is included by topk.hip as well
+// ------------------------------------------------------------------------------------------
+// Launched with 64, 128 or 256 threads and lds_slots*8 bytes of dynamic LDS (the distinct-set table): short
+// reads get small workgroups and small tables, so many of them are resident per CU.
+__global__ __launch_bounds__(KM_THREADS) void kmer_kernel(KmerArgs a)
 {
-	const uint64_t head = (32 + 8ull*n + 15)/16*16;
-	uint64_t cap = std::max<uint64_t>(min_cap, 1u << 20);
-	if(sl->result.cap >= head + sizeof(kwage_hit)){ cap = std::max(cap, (sl->result.cap - head)/sizeof(kwage_hit)); }
-	const uint64_t need = head + cap*sizeof(kwage_hit);
-	if(need > sl->result.cap){
-		if(keep_head && sl->result.p && head == sl->head_bytes){
-			void *np = nullptr;
-			const uint64_t want = need + need/4;
-			HIP_TRY(hipMalloc(&np, want));
-			HIP_TRY(hipMemcpyAsync(np, sl->result.p, head, hipMemcpyDeviceToDevice, sl->stream));
-			HIP_TRY(hipStreamSynchronize(sl->stream));
-			(void)hipFree(sl->result.p);
-			sl->result.p = np;
-			sl->result.cap = want;
-		}
-		else{
-			int rc = sl->result.reserve(need);
-			if(rc){ return rc; }
-		}
-		cap = (sl->result.cap - head)/sizeof(kwage_hit);
+	extern __shared__ __attribute__((aligned(16))) unsigned long long lds_tab[];
+	__shared__ uint8_t codes[KM_THREADS + KWAGE_MAX_WORD_LEN];
+	__shared__ uint32_t count, tile_base;
+
+	const uint32_t q = a.chunk_q ? a.chunk_q[blockIdx.x] : blockIdx.x;
+	const uint64_t t_begin = a.chunk_q ? a.chunk_t0[blockIdx.x] : 0;
+	const uint64_t s0 = a.seq_off[q];
+	const uint64_t len = a.seq_off[q + 1] - s0;
+	const uint64_t npos = (len >= a.k) ? (len - a.k + 1) : 0;
+
+	if(npos == 0){    // kwage.cpp:369-371: query too short
+		if(threadIdx.x == 0){ a.nkmer[q] = 0; a.qthr[q] = 0; }
+		return;
 	}
-	char *base = (char*)sl->result.p;
-	sl->d_counters = (uint64_t*)base;
-	sl->d_nkmer = (uint32_t*)(base + 32);
-	sl->d_qthr = (uint32_t*)(base + 32 + 4ull*n);
-	sl->d_hits = (kwage_hit*)(base + head);
-	sl->hit_cap = cap;
-	sl->head_bytes = head;
-	return KWAGE_OK;
+
+	if(a.shared_lg){
+		kmer_body<false, false>(a, q, s0, len, 0, npos, a.g_tables, a.shared_lg, codes, &count, &tile_base);
+		return;
+	}
+	const uint32_t lg = table_log2(npos);
+	if((1ull << lg) <= a.lds_slots){
+		kmer_body<true, false>(a, q, s0, len, 0, npos, lds_tab, lg, codes, &count, &tile_base);
+	}
+	else if(npos <= KM_CHUNK){
+		kmer_body<false, false>(a, q, s0, len, 0, npos, a.g_tables + a.tab_off[q], lg, codes, &count, &tile_base);
+	}
+	else{             // one of several workgroups on this query (the host cut it the same way, batch_prepare)
+		kmer_body<false, true>(a, q, s0, len, t_begin, min(npos, t_begin + (uint64_t)KM_CHUNK), a.g_tables + a.tab_off[q], lg, codes, &count, &tile_base);
+	}
 }
 
-uint32_t host_table_log2(uint64_t npos)
+// Thresholds after a launch in which long queries were counted by several workgroups (kwage.cpp:388 again: the
+// single-workgroup queries have written the same value already).
+__global__ __launch_bounds__(256) void kmer_finish_kernel(KmerArgs a, uint32_t n_queries)
+{
+	const uint32_t q = blockIdx.x*blockDim.x + threadIdx.x;
+	if(q < n_queries){ a.qthr[q] = a.complete_match ? 0u : (uint32_t)__fmul_rn(a.threshold, (float)a.nkmer[q]); }
+}
+
+// Sparse groups (kwage_group_create_sparse): the matrix holds only the rows listed in `map` (ascending).  Translate
+// every VALID row index of the batch (the first nkmer[q]*num_hash entries of query q) into its position in the list;
+// an index that is not listed is a caller error and is counted in *missing.  wgs_per_query workgroups per query.
+__global__ __launch_bounds__(256) void remap_rows_kernel(uint32_t *rows, const uint64_t *pos_off, const uint32_t *nkmer, uint32_t num_hash,
+                                                         const uint32_t *map, uint32_t map_len, unsigned long long *missing, uint32_t wgs_per_query)
+{
+	const uint32_t q = blockIdx.x / wgs_per_query, part = blockIdx.x % wgs_per_query;      // long queries are shared by several workgroups
+	uint32_t *rq = rows + pos_off[q]*num_hash;
+	const uint64_t n = (uint64_t)nkmer[q]*num_hash;
+	for(uint64_t e = (uint64_t)part*blockDim.x + threadIdx.x; e < n; e += (uint64_t)wgs_per_query*blockDim.x){
+		const uint32_t r = rq[e];
+		uint32_t lo = 0, hi = map_len;                  // first position with map[pos] >= r
+		while(lo < hi){
+			const uint32_t mid = lo + (hi - lo)/2;
+			if(map[mid] < r){ lo = mid + 1; } else { hi = mid; }
+		}
+		if(lo < map_len && map[lo] == r){ rq[e] = lo; }
+		else{ rq[e] = 0; atomicAdd(missing, 1ull); }
+	}
+}
+
+// (a wave takes every nw-th cluster, four at a time: the four records, then the four sets of masks are requested together;
+// the records found go through the wave's LDS buffer and are reserved ONCE per wave -- 150 k clusters with a hit each,
+// reserved one by one, were 1.8 ms of returning atomics on the one hit counter)
+__global__ __launch_bounds__(SEARCH_THREADS) void and_refine_emit_kernel(SearchArgs a, RefineArgs ra)
+{
+	constexpr int B = 4;
+	__shared__ WaveHitBuf hit_bufs[SEARCH_THREADS/WAVE];
+	WaveHitBuf *hbuf = &hit_bufs[threadIdx.x >> 6];
+	WaveHitState hst;
+	const uint32_t lane = threadIdx.x & (WAVE - 1), l = lane & 7u, g = lane >> 3;
+	const uint32_t n_clusters = refine_list_end(ra, 0);
+	const uint32_t gw = __builtin_amdgcn_readfirstlane(blockIdx.x*(blockDim.x/WAVE) + (threadIdx.x >> 6));
+	const uint32_t nw = gridDim.x*(blockDim.x/WAVE);
+	for(uint64_t c0 = gw; c0 < n_clusters; c0 += (uint64_t)B*nw){
+		RefineCluster cl[B];
+		u32x4 m[B];
+#pragma unroll
+		for(int k = 0; k < B; ++k){
+			const uint64_t ci = c0 + (uint64_t)k*nw;
+			cl[k].q = REFINE_NONE;
+			if(ci < n_clusters){ cl[k] = ra.clusters[ci]; }
+		}
+#pragma unroll
+		for(int k = 0; k < B; ++k){
+			const uint32_t groups = cl[k].kstep_groups & 0xFFu;
+			m[k] = (u32x4)(0u);
+			if(cl[k].q != REFINE_NONE && ((groups >> g) & 1u)){          // this lane's 128-byte group of the KiB-step is an item
+				const uint32_t it = cl[k].first_item + __popc(groups & ((1u << g) - 1u));
+				m[k] = reinterpret_cast<const u32x4*>(ra.masks)[(uint64_t)it*8 + l];
+			}
+		}
+#pragma unroll
+		for(int k = 0; k < B; ++k){
+			if(cl[k].q == REFINE_NONE){ continue; }
+			const uint32_t kstep = cl[k].kstep_groups >> 8;
+			emit_masked_hits_buffered(a, hbuf, hst, cl[k].q, kstep*WAVE + lane, m[k], cl[k].n, (uint64_t)cl[k].q*a.runs_per_query + kstep);
+		}
+	}
+	wave_hits_flush(a, hbuf, hst);
+}
+
+// The rows of query q, bucketed by band IN PLACE of the query's stretch of the row list: rows2[pos_off[q]*nh + loc[q][b] ...
+// + loc[q][b+1]) are q's rows in band b (loc is [n_queries][bands + 1], loc[q][bands] = q's rows).  One workgroup per query;
+// the order inside a bucket is free.
+__global__ __launch_bounds__(256) void band_bucket_kernel(const uint32_t *__restrict__ rows, const uint64_t *__restrict__ pos_off, const uint32_t *__restrict__ nkmer,
+                                                         uint32_t num_hash, uint32_t bands, uint32_t rows_per_band, uint32_t *__restrict__ loc, uint32_t *__restrict__ rows2)
+{
+	__shared__ uint32_t h[BAND_MAX], cur[BAND_MAX];
+	const uint32_t q = blockIdx.x;
+	if(threadIdx.x < BAND_MAX){ h[threadIdx.x] = 0; }
+	__syncthreads();
+	const uint64_t base = pos_off[q]*num_hash;
+	const uint32_t n = nkmer[q]*num_hash;
+	for(uint32_t i = threadIdx.x; i < n; i += blockDim.x){
+		atomicAdd(&h[min(rows[base + i]/rows_per_band, bands - 1)], 1u);
+	}
+	__syncthreads();
+	if(threadIdx.x == 0){
+		uint32_t *lq = loc + (uint64_t)q*(bands + 1);
+		uint32_t run = 0;
+		for(uint32_t b = 0; b < bands; ++b){ cur[b] = run; lq[b] = run; run += h[b]; }
+		lq[bands] = run;
+	}
+	__syncthreads();
+	for(uint32_t i = threadIdx.x; i < n; i += blockDim.x){
+		const uint32_t r = rows[base + i];
+		rows2[base + atomicAdd(&cur[min(r/rows_per_band, bands - 1)], 1u)] = r;
+	}
+}
+
+// Second pass of the segmented AND: one thread per (query, 16-byte unit).
+__global__ __launch_bounds__(256) void and_combine_kernel(SearchArgs a)
+{
+	const uint32_t u0 = blockIdx.x*blockDim.x + threadIdx.x;
+	const uint32_t q = blockIdx.y;
+	const uint32_t n = a.nkmer[q];
+	if(n == 0){ return; }                                  // uniform per workgroup
+	const bool on = (u0 < a.units_per_row);
+	const uint32_t unit = on ? u0 : 0;
+	const u32x4 acc = reinterpret_cast<const u32x4*>(a.partial)[(uint64_t)q*a.units_per_row + unit];
+	emit_mask_hits(a, q, unit, acc, n, (uint64_t)q*a.runs_per_query + u0/WAVE, on);      // (a wave = 64 consecutive units of one query)
+}
+
+// Streaming read of the matrix: the box's achievable HBM read rate, reported beside every roofline number.  Every wave
+// walks a contiguous region of its own, eight 1-KiB loads in flight (tools/micro/power_probe.hip: this pattern streams
+// 6.9 TB/s where a grid-stride walk -- round 1/2's probe -- measured 6.4 on the same box; a random-row gather reaches
+// 6.7 TB/s of touched bytes).
+__global__ __launch_bounds__(256) void stream_read_kernel(const u32x4 *src, uint64_t n16, uint32_t *sink)
+{
+	u32x4 acc = (u32x4)(0u);
+	const uint64_t nwaves = (uint64_t)gridDim.x*(blockDim.x/WAVE);
+	const uint64_t wave = (uint64_t)blockIdx.x*(blockDim.x/WAVE) + (threadIdx.x >> 6);
+	const uint64_t per = (n16/nwaves)/(WAVE*8)*(WAVE*8);                 // whole 8 KiB steps; the remainder is left unread
+	const u32x4 *p = src + wave*per + (threadIdx.x & (WAVE - 1));
+	for(uint64_t i = 0; i < per; i += WAVE*8){
+		u32x4 a[8];
+#pragma unroll
+		for(int u = 0; u < 8; ++u){ a[u] = __builtin_nontemporal_load(p + i + u*WAVE); }
+#pragma unroll
+		for(int u = 0; u < 8; ++u){ acc ^= a[u]; }
+	}
+	if((acc.x ^ acc.y ^ acc.z ^ acc.w) == 0x12345678u){ *sink = 1; }   // keep the loads alive
+}
+
+// ------------------------------------------------------------------------------------------
+// The stages kwage_search shares with kwage_search_topk (topk.hip; declared in engine_state.hpp)
+// ------------------------------------------------------------------------------------------
+static uint32_t host_table_log2(uint64_t npos)
 {
 	uint32_t lg = 6;
 	while((1ull << lg) < 2*npos){ ++lg; }
@@ -147,7 +287,137 @@ int batch_prepare(kwage_batch *b, uint32_t k, const KmerLayout **out)
 	return KWAGE_OK;
 }
 
-// Launch the k-mer stage on the ctx stream. rows/kmers_out may be null.
+// The k-mer stage of a search of either kind on stream `s`: distinct canonical k-mers, row indices and the floor
+// (unsigned)(t * n) of every query (0 where complete_match is set: the AND path has no floor).  The caller owns what
+// `o` points to and has filled o.tables with KM_EMPTY.
+int launch_kmer_kernels(const kwage_params &p, const kwage_batch *b, const KmerLayout *L, float threshold, int complete_match,
+                        const KmerStageOut &o, hipStream_t s)
+{
+	if(b->n == 0){ return KWAGE_OK; }
+	KmerArgs a;
+	a.seqs = b->d_seqs;
+	a.seq_off = b->d_seq_off;
+	a.pos_off = L->d_pos_off;
+	a.tab_off = L->d_tab_off;
+	a.g_tables = o.tables;
+	a.k = p.kmer_len;
+	a.num_hash = p.num_hash;
+	a.row_mask = (p.log_2_filter_len >= 32) ? 0xFFFFFFFFu : ((1u << p.log_2_filter_len) - 1u);
+	a.threshold = threshold;
+	a.complete_match = complete_match;
+	a.rows = o.rows;
+	a.kmers_out = o.kmers;
+	a.nkmer = o.nkmer;
+	a.qthr = o.qthr;
+	a.total_kmers = nullptr;           // summed on the host from nkmer[] (a per-workgroup atomic serialises)
+	a.shared_lg = 0;
+	a.bloom_bits = nullptr;
+	a.chunk_q = L->d_chunk_q;
+	a.chunk_t0 = L->d_chunk_t0;
+	if(L->multi_chunk){      // the chunks of a long query add their new k-mers into nkmer[q]
+		HIP_TRY(hipMemsetAsync(o.nkmer, 0, (size_t)b->n*sizeof(uint32_t), s));
+	}
+	// workgroup and LDS table sized for the longest query of the batch: queries whose table would not fit
+	// KM_LDS_SLOTS use the global tables laid out by batch_prepare (same rule there)
+	uint32_t slots = 64;
+	while(slots < KM_LDS_SLOTS && slots < 2*L->max_pos){ slots *= 2; }
+	a.lds_slots = slots;
+	const uint32_t threads = (L->max_pos <= 192) ? 64 : (L->max_pos <= 768) ? 128 : KM_THREADS;
+	hipLaunchKernelGGL(kmer_kernel, dim3((uint32_t)L->n_chunks), dim3(threads), (size_t)slots*sizeof(uint64_t), s, a);
+	HIP_TRY(hipGetLastError());
+	if(L->multi_chunk){      // thresholds of the queries whose k-mers were counted by several workgroups
+		hipLaunchKernelGGL(kmer_finish_kernel, dim3((b->n + 255)/256), dim3(256), 0, s, a, b->n);
+		HIP_TRY(hipGetLastError());
+	}
+	return KWAGE_OK;
+}
+
+// Sparse group: row index -> position in the group's row list, for the n_queries (> 0) row lists the k-mer stage left in
+// d_rows; *d_missing counts the indices that are not listed.
+// (a workgroup per 4096 row indices of the longest query, so that a genome-length query is not one workgroup's job)
+int launch_remap_rows(const kwage_group *g, uint32_t n_queries, const KmerLayout *L, uint32_t *d_rows, const uint32_t *d_nkmer,
+                      unsigned long long *d_missing, hipStream_t s)
+{
+	const uint32_t nh = g->params.num_hash;
+	const uint64_t per_q = std::max<uint64_t>(1, (L->max_pos*nh + 4095)/4096);
+	const uint64_t wgs_per_q = std::min<uint64_t>(per_q, std::max<uint64_t>(1, 0x7FFFFFFFull/n_queries));
+	hipLaunchKernelGGL(remap_rows_kernel, dim3((uint32_t)(n_queries*wgs_per_q)), dim3(256), 0, s, d_rows, L->d_pos_off, d_nkmer,
+	                   nh, g->d_row_map, (uint32_t)g->h_row_map.size(), d_missing, (uint32_t)wgs_per_q);
+	HIP_TRY(hipGetLastError());
+	return KWAGE_OK;
+}
+
+// counter planes for counts up to `max_count`: the smallest instantiated size whose bits hold it
+uint32_t planes_for(uint64_t max_count)
+{
+	uint32_t bits = 1;
+	while(bits < 32 && (max_count >> bits) != 0){ ++bits; }
+	return (bits <= 7) ? 7 : (bits <= 10) ? 10 : (bits <= 14) ? 14 : (bits <= 20) ? 20 : 32;
+}
+
+// How many segments to cut each query's k-mer list into: none while the launch already has
+// enough waves to fill the chip; otherwise enough to reach ~TARGET_TILES waves (about 8 per CU, ~2x the bytes in flight that cover HBM latency), but never segments
+// shorter than MIN_SEG_KMERS k-mers.  The force_segs knob forces a count (tests).
+void choose_segments(SearchArgs &a, uint64_t max_kmers, uint64_t max_segs, int64_t force_segs)
+{
+	static const uint64_t TARGET_TILES = 2048, MIN_SEG_KMERS = 64;
+	const uint64_t MAX_SEGS = max_segs;
+	a.segs = 1;
+	a.seg_kmers = (uint32_t)std::max<uint64_t>(max_kmers, 1);
+	uint64_t want = 1;
+	if(force_segs > 0){ want = (uint64_t)force_segs; }
+	else{
+		const uint64_t tiles = (uint64_t)a.n_queries*a.chunks;
+		if(tiles >= TARGET_TILES || max_kmers < 2*MIN_SEG_KMERS){ return; }
+		want = std::min<uint64_t>((TARGET_TILES + tiles - 1)/tiles, max_kmers/MIN_SEG_KMERS);
+	}
+	want = std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint64_t>(want, MAX_SEGS), std::max<uint64_t>(max_kmers, 1)));
+	if(want <= 1){ return; }
+	a.seg_kmers = (uint32_t)((max_kmers + want - 1)/want);
+	a.segs = (uint32_t)((max_kmers + a.seg_kmers - 1)/a.seg_kmers);
+}
+
+}  // namespace kwage
+
+namespace {
+
+// Lay the result block out for n queries and at least min_cap hit records. Growing the block keeps
+// its head (counters + per-query arrays) when keep_head is set (hit-buffer growth mid-search).
+int layout_result(Slot *sl, uint32_t n, uint64_t min_cap, bool keep_head)
+{
+	const uint64_t head = (32 + 8ull*n + 15)/16*16;
+	uint64_t cap = std::max<uint64_t>(min_cap, 1u << 20);
+	if(sl->result.cap >= head + sizeof(kwage_hit)){ cap = std::max(cap, (sl->result.cap - head)/sizeof(kwage_hit)); }
+	const uint64_t need = head + cap*sizeof(kwage_hit);
+	if(need > sl->result.cap){
+		if(keep_head && sl->result.p && head == sl->head_bytes){
+			void *np = nullptr;
+			const uint64_t want = need + need/4;
+			HIP_TRY(hipMalloc(&np, want));
+			HIP_TRY(hipMemcpyAsync(np, sl->result.p, head, hipMemcpyDeviceToDevice, sl->stream));
+			HIP_TRY(hipStreamSynchronize(sl->stream));
+			(void)hipFree(sl->result.p);
+			sl->result.p = np;
+			sl->result.cap = want;
+		}
+		else{
+			int rc = sl->result.reserve(need);
+			if(rc){ return rc; }
+		}
+		cap = (sl->result.cap - head)/sizeof(kwage_hit);
+	}
+	char *base = (char*)sl->result.p;
+	sl->d_counters = (uint64_t*)base;
+	sl->d_nkmer = (uint32_t*)(base + 32);
+	sl->d_qthr = (uint32_t*)(base + 32 + 4ull*n);
+	sl->d_hits = (kwage_hit*)(base + head);
+	sl->hit_cap = cap;
+	sl->head_bytes = head;
+	return KWAGE_OK;
+}
+
+// The threshold search's k-mer stage on the slot's stream: result layout, table reservation, counter clear, then the
+// kernels. rows/kmers_out may be null.
 int launch_kmer_stage(Slot *sl, const kwage_params &p, kwage_batch *b, const KmerLayout *L, float threshold,
                       uint32_t *d_rows, uint64_t *d_kmers)
 {
@@ -158,44 +428,8 @@ int launch_kmer_stage(Slot *sl, const kwage_params &p, kwage_batch *b, const Kme
 		HIP_TRY(hipMemsetAsync(sl->tables.p, 0xFF, L->table_slots*sizeof(uint64_t), sl->stream));
 	}
 	HIP_TRY(hipMemsetAsync(sl->d_counters, 0, 4*sizeof(uint64_t), sl->stream));
-	if(b->n == 0){ return KWAGE_OK; }
-
-	KmerArgs a;
-	a.seqs = b->d_seqs;
-	a.seq_off = b->d_seq_off;
-	a.pos_off = L->d_pos_off;
-	a.tab_off = L->d_tab_off;
-	a.g_tables = (unsigned long long*)sl->tables.p;
-	a.k = p.kmer_len;
-	a.num_hash = p.num_hash;
-	a.row_mask = (p.log_2_filter_len >= 32) ? 0xFFFFFFFFu : ((1u << p.log_2_filter_len) - 1u);
-	a.threshold = threshold;
-	a.complete_match = (threshold == 1.0f) ? 1 : 0;      // kwage.cpp:349
-	a.rows = d_rows;
-	a.kmers_out = d_kmers;
-	a.nkmer = sl->d_nkmer;
-	a.qthr = sl->d_qthr;
-	a.total_kmers = nullptr;           // summed on the host from nkmer[] (a per-workgroup atomic serialises)
-	a.shared_lg = 0;
-	a.bloom_bits = nullptr;
-	a.chunk_q = L->d_chunk_q;
-	a.chunk_t0 = L->d_chunk_t0;
-	if(L->multi_chunk){      // the chunks of a long query add their new k-mers into nkmer[q]
-		HIP_TRY(hipMemsetAsync(sl->d_nkmer, 0, (size_t)b->n*sizeof(uint32_t), sl->stream));
-	}
-	// workgroup and LDS table sized for the longest query of the batch: queries whose table would not fit
-	// KM_LDS_SLOTS use the global tables laid out by batch_prepare (same rule there)
-	uint32_t slots = 64;
-	while(slots < KM_LDS_SLOTS && slots < 2*L->max_pos){ slots *= 2; }
-	a.lds_slots = slots;
-	const uint32_t threads = (L->max_pos <= 192) ? 64 : (L->max_pos <= 768) ? 128 : KM_THREADS;
-	hipLaunchKernelGGL(kmer_kernel, dim3((uint32_t)L->n_chunks), dim3(threads), (size_t)slots*sizeof(uint64_t), sl->stream, a);
-	HIP_TRY(hipGetLastError());
-	if(L->multi_chunk){      // thresholds of the queries whose k-mers were counted by several workgroups
-		hipLaunchKernelGGL(kmer_finish_kernel, dim3((b->n + 255)/256), dim3(256), 0, sl->stream, a, b->n);
-		HIP_TRY(hipGetLastError());
-	}
-	return KWAGE_OK;
+	const KmerStageOut o = {d_rows, d_kmers, sl->d_nkmer, sl->d_qthr, (unsigned long long*)sl->tables.p};
+	return launch_kmer_kernels(p, b, L, threshold, (threshold == 1.0f) ? 1 : 0, o, sl->stream);      // kwage.cpp:349
 }
 
 // The events of one gather stage, carried by its kernel launches themselves (hipExtLaunchKernelGGL): the first launch of
@@ -312,14 +546,6 @@ void launch_count_nh(const SearchArgs &a, hipStream_t s, const StageEvents &ge)
 	}
 }
 
-// counter planes for counts up to `max_count`: the smallest instantiated size whose bits hold it
-uint32_t planes_for(uint64_t max_count)
-{
-	uint32_t bits = 1;
-	while(bits < 32 && (max_count >> bits) != 0){ ++bits; }
-	return (bits <= 7) ? 7 : (bits <= 10) ? 10 : (bits <= 14) ? 14 : (bits <= 20) ? 20 : 32;
-}
-
 void launch_count_planes(uint32_t planes, const SearchArgs &a, hipStream_t s, const StageEvents &ge)
 {
 	switch(planes){
@@ -400,28 +626,9 @@ int launch_count_combine(const SearchArgs &a, uint32_t seg_planes, hipStream_t s
 	return KWAGE_OK;
 }
 
-// How many segments to cut each query's k-mer list into: none while the launch already has
-// enough waves to fill the chip; otherwise enough to reach ~TARGET_TILES waves (about 8 per CU, ~2x the bytes in flight that cover HBM latency), but never segments
-// shorter than MIN_SEG_KMERS k-mers.  The force_segs knob forces a count (tests).
-void choose_segments(SearchArgs &a, uint64_t max_kmers, uint64_t max_segs, int64_t force_segs)
-{
-	static const uint64_t TARGET_TILES = 2048, MIN_SEG_KMERS = 64;
-	const uint64_t MAX_SEGS = max_segs;
-	a.segs = 1;
-	a.seg_kmers = (uint32_t)std::max<uint64_t>(max_kmers, 1);
-	if(a.n_queries > 65535){ return; }      // the combine kernels index queries with gridDim.y
-	uint64_t want = 1;
-	if(force_segs > 0){ want = (uint64_t)force_segs; }
-	else{
-		const uint64_t tiles = (uint64_t)a.n_queries*a.chunks;
-		if(tiles >= TARGET_TILES || max_kmers < 2*MIN_SEG_KMERS){ return; }
-		want = std::min<uint64_t>((TARGET_TILES + tiles - 1)/tiles, max_kmers/MIN_SEG_KMERS);
-	}
-	want = std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint64_t>(want, MAX_SEGS), std::max<uint64_t>(max_kmers, 1)));
-	if(want <= 1){ return; }
-	a.seg_kmers = (uint32_t)((max_kmers + want - 1)/want);
-	a.segs = (uint32_t)((max_kmers + a.seg_kmers - 1)/a.seg_kmers);
-}
+// The segment limit of a launch of this search: its combine kernels index queries with gridDim.y, so no segments above
+// 65535 queries.
+uint64_t max_segments(const SearchArgs &a, uint64_t max_segs) { return (a.n_queries > 65535) ? 1 : max_segs; }
 
 // A scratch buffer the kernels leave all zero: cleared when it is (re)allocated, never per search.
 int reserve_zeroed(DevBuf &buf, uint64_t bytes, hipStream_t s)
@@ -549,7 +756,7 @@ int launch_search_stage(Slot *sl, kwage_group *g, kwage_batch *b, const KmerLayo
 		const bool wide_rows = wide_ok && a.units_per_row > (uint32_t)std::max<int64_t>(tn.and_wide_min_kib, 1)*WAVE;
 		const AndCfg cfg = and_config(tn, a.units_per_row, wide_rows);
 		a.chunks = (a.units_per_row + WAVE*cfg.vec - 1)/(WAVE*cfg.vec);
-		choose_segments(a, L->max_pos, 4096, tn.force_segs);
+		choose_segments(a, L->max_pos, max_segments(a, 4096), tn.force_segs);
 		if((uint64_t)a.n_queries*a.segs*a.chunks/4 + 1 > 0x7FFFFFFFull){ return fail(KWAGE_ERR_ARG, "batch too large for one launch"); }
 		// narrow rows: several queries per wave (tools/bench_narrow.py)
 		if(tn.narrow && a.segs == 1 && a.units_per_row <= 32 && a.n_queries >= 64){
@@ -869,7 +1076,7 @@ int launch_search_stage(Slot *sl, kwage_group *g, kwage_batch *b, const KmerLayo
 		// Long queries: segments of the k-mer list are counted by different waves into a slab of partial counters
 		// and added by count_combine_kernel (a tree per (query, 64 units)); a segment's counters need only the
 		// planes its own k-mer count can reach.
-		choose_segments(a, L->max_pos, 1024, tn.force_segs);
+		choose_segments(a, L->max_pos, max_segments(a, 1024), tn.force_segs);
 		uint32_t seg_planes = (a.segs > 1) ? planes_for(a.seg_kmers) : planes;
 		// keep the slab of partial counters bounded (1 GiB)
 		while(a.segs > 1 && (uint64_t)a.n_queries*a.segs*seg_planes*g->stride > (1ull << 30)){
@@ -1034,13 +1241,8 @@ int submit_search(Slot *sl, kwage_group *g, kwage_batch *b, float threshold, uin
 	const bool timing_kmer = (flags & KWAGE_SEARCH_TIMING) && (flags & KWAGE_SEARCH_TIMING_KMER);
 	if(timing_kmer){ HIP_TRY(hipEventRecord(sl->ev[0], sl->stream)); }
 	if((rc = launch_kmer_stage(sl, g->params, b, L, threshold, (uint32_t*)sl->rows.p, nullptr))){ return rc; }
-	if(g->d_row_map && b->n){      // sparse group: row index -> position in the group's row list (counter 2 = indices not listed)
-		// (a workgroup per 4096 row indices of the longest query, so that a genome-length query is not one workgroup's job)
-		const uint64_t per_q = std::max<uint64_t>(1, (L->max_pos*g->params.num_hash + 4095)/4096);
-		const uint64_t wgs_per_q = std::min<uint64_t>(per_q, std::max<uint64_t>(1, 0x7FFFFFFFull/b->n));
-		hipLaunchKernelGGL(remap_rows_kernel, dim3((uint32_t)(b->n*wgs_per_q)), dim3(256), 0, sl->stream, (uint32_t*)sl->rows.p, L->d_pos_off, sl->d_nkmer,
-		                   g->params.num_hash, g->d_row_map, (uint32_t)g->h_row_map.size(), (unsigned long long*)sl->d_counters + 2, (uint32_t)wgs_per_q);
-		HIP_TRY(hipGetLastError());
+	if(g->d_row_map && b->n){      // sparse group (counter 2 = indices not listed)
+		if((rc = launch_remap_rows(g, b->n, L, (uint32_t*)sl->rows.p, sl->d_nkmer, (unsigned long long*)sl->d_counters + 2, sl->stream))){ return rc; }
 	}
 	if(timing_kmer){ HIP_TRY(hipEventRecord(sl->ev[1], sl->stream)); }
 	if((rc = enqueue_search_and_copy(sl))){ return rc; }
@@ -1478,16 +1680,6 @@ void sort_hits(kwage_hit *hits, size_t n)
 		}
 	});
 }
-
-struct ResultStorage {
-	kwage_result pub;
-	std::unique_ptr<kwage_hit[]> hits;            // short lists
-	std::shared_ptr<PinnedPool> pool;             // long lists: a pinned block of the context's pool
-	PinBuf pinned;
-	std::vector<uint32_t> nkmer, qthr;
-	char kernel[64];
-	~ResultStorage() { if(pool){ pool->release(pinned); } }
-};
 
 // Build the host result of a collected search from the slot's staging buffer.
 int build_result(Slot *sl, kwage_group *g, kwage_batch *b, const SearchOutcome &so, kwage_result **out)

@@ -4,6 +4,8 @@
 //
 //   engine.hip   contexts, tuning knobs, query batches, the search pipeline (k-mer stage, gather kernels, hit lists)
 //   loader.hip   database groups: allocation, the loaders (.db files raw and compressed, sparse groups), synthetic columns
+//   topk.hip     the top-k search: engine.hip's batch layout, k-mer stage, counter widths, segment rule and result block
+//                (declared at the end of this file), then its own selection kernels
 #ifndef KWAGE_AMD_ENGINE_STATE_HPP
 #define KWAGE_AMD_ENGINE_STATE_HPP
 
@@ -442,6 +444,48 @@ inline int set_device(kwage_ctx *ctx)
 // loader.hip, called where a context is created and destroyed
 void find_numa_cpus(int device, int *node, std::vector<int> *cpus);
 void release_mapping(kwage_ctx *ctx);
+
+// engine.hip: the stages kwage_search (engine.hip) and kwage_search_topk (topk.hip) both run, and the result both return
+
+struct SearchArgs;      // kernels.hpp
+
+// The batch's layout for k-mer length k, built on first use and kept with the batch: a search of either kind finds the
+// one an earlier search left.
+int batch_prepare(kwage_batch *b, uint32_t k, const KmerLayout **out);
+
+// What the k-mer stage writes, owned by the caller: the row indices and the distinct words (either may be null), the
+// k-mer count and the floor of every query, and the global distinct sets of the layout's long queries (table_slots words
+// filled with 0xFF by the caller; unused when the layout has none).
+struct KmerStageOut {
+	uint32_t *rows;
+	uint64_t *kmers;
+	uint32_t *nkmer, *qthr;
+	unsigned long long *tables;
+};
+// kmer_kernel (and kmer_finish_kernel for a layout with multi-chunk queries, after clearing o.nkmer) on stream s.
+// complete_match: every floor is 0 (the threshold search at t = 1); otherwise (unsigned)(threshold * n).
+int launch_kmer_kernels(const kwage_params &p, const kwage_batch *b, const KmerLayout *L, float threshold, int complete_match,
+                        const KmerStageOut &o, hipStream_t s);
+// Sparse groups: remap_rows_kernel over the row lists of n_queries (> 0) queries; *d_missing counts indices not listed.
+int launch_remap_rows(const kwage_group *g, uint32_t n_queries, const KmerLayout *L, uint32_t *d_rows, const uint32_t *d_nkmer,
+                      unsigned long long *d_missing, hipStream_t s);
+
+// The narrowest instantiated counter width (7, 10, 14, 20 or 32 planes) whose bits hold max_count.
+uint32_t planes_for(uint64_t max_count);
+// Sets a.segs / a.seg_kmers from a.n_queries and a.chunks: how many segments each query's k-mer list is cut into, at
+// most max_segs (force_segs > 0: the tuning knob's count instead of the rule's).
+void choose_segments(SearchArgs &a, uint64_t max_kmers, uint64_t max_segs, int64_t force_segs);
+
+// What a kwage_result* points into, for every search kind: kwage_result_free() deletes it.
+struct ResultStorage {
+	kwage_result pub;                             // first member: the pointer the caller holds
+	std::unique_ptr<kwage_hit[]> hits;            // short lists
+	std::shared_ptr<PinnedPool> pool;             // long lists: a pinned block of the context's pool
+	PinBuf pinned;
+	std::vector<uint32_t> nkmer, qthr;
+	char kernel[64];
+	~ResultStorage() { if(pool){ pool->release(pinned); } }
+};
 
 }  // namespace kwage
 

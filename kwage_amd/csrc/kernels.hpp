@@ -1,9 +1,9 @@
 // kwage_amd/csrc/kernels.hpp -- hand-written gfx950 (CDNA4, wave64) kernels of the kwage
 // search path.  Integer / bit work only, HBM-bandwidth bound: no MFMA anywhere.
 //
-//   kmer_kernel   word.h:73-104,161-165 (2-bit canonical k-mers) + kwage.cpp:362-366 (distinct
+//   kmer_body     word.h:73-104,161-165 (2-bit canonical k-mers) + kwage.cpp:362-366 (distinct
 //                 set) + hash.cpp:176-234 (MurmurHash3_x86_32 of the ASCII k-mer) + kwage.cpp:411-412
-//                 (row index) + kwage.cpp:388 (float32 threshold).
+//                 (row index) + kwage.cpp:388 (float32 threshold): the body of kmer_kernel.
 //   and_kernel    kwage.cpp:404-470 at threshold == 1.0f: gather the addressed bit-slice rows,
 //                 AND them (bloom.h:245-262), extract hits (kwage.cpp:489-538).
 //   and_walk_kernel  the same reduction for rows of 3..16 KiB: a persistent grid, every wave walks an equal share
@@ -17,6 +17,11 @@
 // A wave owns a "tile" = (query, 64*VEC*16 contiguous bytes of every addressed row): each lane
 // holds VEC 16-byte vectors, so one global_load_dwordx4 per lane reads 1 KiB of a row per wave,
 // fully coalesced; UNROLL rows are kept in flight per wave.
+//
+// Everything here is a template, a __forceinline__ device function or a plain struct, so that two translation units can
+// include it: engine.hip (kwage_search) and topk.hip (kwage_search_topk, which builds on SearchArgs, count_kmers and
+// count_kernel's SEG form).  The seven kernels of the search that are not templates are defined once, in engine.hip,
+// the only unit that launches them; each is named here at the place it belongs to.
 #ifndef KWAGE_AMD_KERNELS_HPP
 #define KWAGE_AMD_KERNELS_HPP
 
@@ -175,69 +180,7 @@ __device__ __forceinline__ void kmer_body(const KmerArgs &a, uint32_t q, uint64_
 	}
 }
 
-// Launched with 64, 128 or 256 threads and lds_slots*8 bytes of dynamic LDS (the distinct-set table): short
-// reads get small workgroups and small tables, so many of them are resident per CU.
-__global__ __launch_bounds__(KM_THREADS) void kmer_kernel(KmerArgs a)
-{
-	extern __shared__ __attribute__((aligned(16))) unsigned long long lds_tab[];
-	__shared__ uint8_t codes[KM_THREADS + KWAGE_MAX_WORD_LEN];
-	__shared__ uint32_t count, tile_base;
-
-	const uint32_t q = a.chunk_q ? a.chunk_q[blockIdx.x] : blockIdx.x;
-	const uint64_t t_begin = a.chunk_q ? a.chunk_t0[blockIdx.x] : 0;
-	const uint64_t s0 = a.seq_off[q];
-	const uint64_t len = a.seq_off[q + 1] - s0;
-	const uint64_t npos = (len >= a.k) ? (len - a.k + 1) : 0;
-
-	if(npos == 0){    // kwage.cpp:369-371: query too short
-		if(threadIdx.x == 0){ a.nkmer[q] = 0; a.qthr[q] = 0; }
-		return;
-	}
-
-	if(a.shared_lg){
-		kmer_body<false, false>(a, q, s0, len, 0, npos, a.g_tables, a.shared_lg, codes, &count, &tile_base);
-		return;
-	}
-	const uint32_t lg = table_log2(npos);
-	if((1ull << lg) <= a.lds_slots){
-		kmer_body<true, false>(a, q, s0, len, 0, npos, lds_tab, lg, codes, &count, &tile_base);
-	}
-	else if(npos <= KM_CHUNK){
-		kmer_body<false, false>(a, q, s0, len, 0, npos, a.g_tables + a.tab_off[q], lg, codes, &count, &tile_base);
-	}
-	else{             // one of several workgroups on this query (the host cut it the same way, batch_prepare)
-		kmer_body<false, true>(a, q, s0, len, t_begin, min(npos, t_begin + (uint64_t)KM_CHUNK), a.g_tables + a.tab_off[q], lg, codes, &count, &tile_base);
-	}
-}
-
-// Thresholds after a launch in which long queries were counted by several workgroups (kwage.cpp:388 again: the
-// single-workgroup queries have written the same value already).
-__global__ __launch_bounds__(256) void kmer_finish_kernel(KmerArgs a, uint32_t n_queries)
-{
-	const uint32_t q = blockIdx.x*blockDim.x + threadIdx.x;
-	if(q < n_queries){ a.qthr[q] = a.complete_match ? 0u : (uint32_t)__fmul_rn(a.threshold, (float)a.nkmer[q]); }
-}
-
-// Sparse groups (kwage_group_create_sparse): the matrix holds only the rows listed in `map` (ascending).  Translate
-// every VALID row index of the batch (the first nkmer[q]*num_hash entries of query q) into its position in the list;
-// an index that is not listed is a caller error and is counted in *missing.  wgs_per_query workgroups per query.
-__global__ __launch_bounds__(256) void remap_rows_kernel(uint32_t *rows, const uint64_t *pos_off, const uint32_t *nkmer, uint32_t num_hash,
-                                                         const uint32_t *map, uint32_t map_len, unsigned long long *missing, uint32_t wgs_per_query)
-{
-	const uint32_t q = blockIdx.x / wgs_per_query, part = blockIdx.x % wgs_per_query;      // long queries are shared by several workgroups
-	uint32_t *rq = rows + pos_off[q]*num_hash;
-	const uint64_t n = (uint64_t)nkmer[q]*num_hash;
-	for(uint64_t e = (uint64_t)part*blockDim.x + threadIdx.x; e < n; e += (uint64_t)wgs_per_query*blockDim.x){
-		const uint32_t r = rq[e];
-		uint32_t lo = 0, hi = map_len;                  // first position with map[pos] >= r
-		while(lo < hi){
-			const uint32_t mid = lo + (hi - lo)/2;
-			if(map[mid] < r){ lo = mid + 1; } else { hi = mid; }
-		}
-		if(lo < map_len && map[lo] == r){ rq[e] = lo; }
-		else{ rq[e] = 0; atomicAdd(missing, 1ull); }
-	}
-}
+// (kmer_kernel, which picks the kmer_body form per workgroup, kmer_finish_kernel and remap_rows_kernel: engine.hip)
 
 // ------------------------------------------------------------------------------------------
 // search kernels
@@ -870,46 +813,7 @@ __global__ __launch_bounds__(SEARCH_THREADS) void and_refine_kernel(SearchArgs a
 	}
 }
 
-// (a wave takes every nw-th cluster, four at a time: the four records, then the four sets of masks are requested together;
-// the records found go through the wave's LDS buffer and are reserved ONCE per wave -- 150 k clusters with a hit each,
-// reserved one by one, were 1.8 ms of returning atomics on the one hit counter)
-__global__ __launch_bounds__(SEARCH_THREADS) void and_refine_emit_kernel(SearchArgs a, RefineArgs ra)
-{
-	constexpr int B = 4;
-	__shared__ WaveHitBuf hit_bufs[SEARCH_THREADS/WAVE];
-	WaveHitBuf *hbuf = &hit_bufs[threadIdx.x >> 6];
-	WaveHitState hst;
-	const uint32_t lane = threadIdx.x & (WAVE - 1), l = lane & 7u, g = lane >> 3;
-	const uint32_t n_clusters = refine_list_end(ra, 0);
-	const uint32_t gw = __builtin_amdgcn_readfirstlane(blockIdx.x*(blockDim.x/WAVE) + (threadIdx.x >> 6));
-	const uint32_t nw = gridDim.x*(blockDim.x/WAVE);
-	for(uint64_t c0 = gw; c0 < n_clusters; c0 += (uint64_t)B*nw){
-		RefineCluster cl[B];
-		u32x4 m[B];
-#pragma unroll
-		for(int k = 0; k < B; ++k){
-			const uint64_t ci = c0 + (uint64_t)k*nw;
-			cl[k].q = REFINE_NONE;
-			if(ci < n_clusters){ cl[k] = ra.clusters[ci]; }
-		}
-#pragma unroll
-		for(int k = 0; k < B; ++k){
-			const uint32_t groups = cl[k].kstep_groups & 0xFFu;
-			m[k] = (u32x4)(0u);
-			if(cl[k].q != REFINE_NONE && ((groups >> g) & 1u)){          // this lane's 128-byte group of the KiB-step is an item
-				const uint32_t it = cl[k].first_item + __popc(groups & ((1u << g) - 1u));
-				m[k] = reinterpret_cast<const u32x4*>(ra.masks)[(uint64_t)it*8 + l];
-			}
-		}
-#pragma unroll
-		for(int k = 0; k < B; ++k){
-			if(cl[k].q == REFINE_NONE){ continue; }
-			const uint32_t kstep = cl[k].kstep_groups >> 8;
-			emit_masked_hits_buffered(a, hbuf, hst, cl[k].q, kstep*WAVE + lane, m[k], cl[k].n, (uint64_t)cl[k].q*a.runs_per_query + kstep);
-		}
-	}
-	wave_hits_flush(a, hbuf, hst);
-}
+// (and_refine_emit_kernel: engine.hip)
 
 // threshold == 1.0f, "walk" form of the gather + AND for rows of 3..16 KiB: a wave walks each of its rows over
 // the WHOLE width of a column tile (CH KiB, CH accumulators per lane), UNROLL rows at a time, so a row's
@@ -1134,34 +1038,7 @@ struct BandArgs {
 };
 static constexpr uint32_t BAND_MAX = 64;
 
-// The rows of query q, bucketed by band IN PLACE of the query's stretch of the row list: rows2[pos_off[q]*nh + loc[q][b] ...
-// + loc[q][b+1]) are q's rows in band b (loc is [n_queries][bands + 1], loc[q][bands] = q's rows).  One workgroup per query;
-// the order inside a bucket is free.
-__global__ __launch_bounds__(256) void band_bucket_kernel(const uint32_t *__restrict__ rows, const uint64_t *__restrict__ pos_off, const uint32_t *__restrict__ nkmer,
-                                                         uint32_t num_hash, uint32_t bands, uint32_t rows_per_band, uint32_t *__restrict__ loc, uint32_t *__restrict__ rows2)
-{
-	__shared__ uint32_t h[BAND_MAX], cur[BAND_MAX];
-	const uint32_t q = blockIdx.x;
-	if(threadIdx.x < BAND_MAX){ h[threadIdx.x] = 0; }
-	__syncthreads();
-	const uint64_t base = pos_off[q]*num_hash;
-	const uint32_t n = nkmer[q]*num_hash;
-	for(uint32_t i = threadIdx.x; i < n; i += blockDim.x){
-		atomicAdd(&h[min(rows[base + i]/rows_per_band, bands - 1)], 1u);
-	}
-	__syncthreads();
-	if(threadIdx.x == 0){
-		uint32_t *lq = loc + (uint64_t)q*(bands + 1);
-		uint32_t run = 0;
-		for(uint32_t b = 0; b < bands; ++b){ cur[b] = run; lq[b] = run; run += h[b]; }
-		lq[bands] = run;
-	}
-	__syncthreads();
-	for(uint32_t i = threadIdx.x; i < n; i += blockDim.x){
-		const uint32_t r = rows[base + i];
-		rows2[base + atomicAdd(&cur[min(r/rows_per_band, bands - 1)], 1u)] = r;
-	}
-}
+// (band_bucket_kernel: engine.hip)
 
 // (the grid and a wave's share of the batch's POSITIONS are and_walk_kernel's: wa.total_slots, wa.per_wave; in band b a
 // wave takes, of every query piece it holds, the same fraction of the query's band-b bucket as the piece is of the query)
@@ -1333,18 +1210,7 @@ __global__ __launch_bounds__(SEARCH_THREADS) void and_narrow_kernel(SearchArgs a
 	emit_mask_hits(a, q, unit, acc, n, blockIdx.x, active, &wg_scratch);      // every wave of the workgroup gets here, exactly once (run = the workgroup: queries ascend with waves and lanes)
 }
 
-// Second pass of the segmented AND: one thread per (query, 16-byte unit).
-__global__ __launch_bounds__(256) void and_combine_kernel(SearchArgs a)
-{
-	const uint32_t u0 = blockIdx.x*blockDim.x + threadIdx.x;
-	const uint32_t q = blockIdx.y;
-	const uint32_t n = a.nkmer[q];
-	if(n == 0){ return; }                                  // uniform per workgroup
-	const bool on = (u0 < a.units_per_row);
-	const uint32_t unit = on ? u0 : 0;
-	const u32x4 acc = reinterpret_cast<const u32x4*>(a.partial)[(uint64_t)q*a.units_per_row + unit];
-	emit_mask_hits(a, q, unit, acc, n, (uint64_t)q*a.runs_per_query + u0/WAVE, on);      // (a wave = 64 consecutive units of one query)
-}
+// (and_combine_kernel: engine.hip)
 
 // threshold < 1: count, per column, the k-mers whose every hash row has the bit set
 // (kwage.cpp:404-433 with increment_count, bloom.h:291-330).  Counters are bit-sliced:
@@ -2180,26 +2046,7 @@ __global__ __launch_bounds__(COMBINE_WAVES*WAVE) void count_combine_kernel(Searc
 	if(w == 0){ emit_count_hits<PLANES>(a, q, unit, plane, a.qthr[q], (uint64_t)q*a.runs_per_query + blockIdx.x, on); }
 }
 
-// Streaming read of the matrix: the box's achievable HBM read rate, reported beside every roofline number.  Every wave
-// walks a contiguous region of its own, eight 1-KiB loads in flight (tools/micro/power_probe.hip: this pattern streams
-// 6.9 TB/s where a grid-stride walk -- round 1/2's probe -- measured 6.4 on the same box; a random-row gather reaches
-// 6.7 TB/s of touched bytes).
-__global__ __launch_bounds__(256) void stream_read_kernel(const u32x4 *src, uint64_t n16, uint32_t *sink)
-{
-	u32x4 acc = (u32x4)(0u);
-	const uint64_t nwaves = (uint64_t)gridDim.x*(blockDim.x/WAVE);
-	const uint64_t wave = (uint64_t)blockIdx.x*(blockDim.x/WAVE) + (threadIdx.x >> 6);
-	const uint64_t per = (n16/nwaves)/(WAVE*8)*(WAVE*8);                 // whole 8 KiB steps; the remainder is left unread
-	const u32x4 *p = src + wave*per + (threadIdx.x & (WAVE - 1));
-	for(uint64_t i = 0; i < per; i += WAVE*8){
-		u32x4 a[8];
-#pragma unroll
-		for(int u = 0; u < 8; ++u){ a[u] = __builtin_nontemporal_load(p + i + u*WAVE); }
-#pragma unroll
-		for(int u = 0; u < 8; ++u){ acc ^= a[u]; }
-	}
-	if((acc.x ^ acc.y ^ acc.z ^ acc.w) == 0x12345678u){ *sink = 1; }   // keep the loads alive
-}
+// (stream_read_kernel: engine.hip)
 
 }  // namespace kwage
 

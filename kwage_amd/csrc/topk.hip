@@ -4,10 +4,9 @@
 //   kmer_kernel  ->  topk_tile_kernel                                   ->  topk_merge_kernel  ->  D2H of <= k records per query
 //               |->  count_kernel<SEG> + topk_combine_kernel (long queries)
 //
-// The kernels of kernels.hpp are included into a namespace of their own (topk_dev): the header defines non-inline
-// kernels, and engine.hip has the same definitions at ::kwage -- two external definitions would not link.  This
-// translation unit's copies are private to its code object; the host-side objects (context, group, batch) are
-// engine_state.hpp's, shared with engine.hip.
+// The batch layout, the k-mer stage, the counter widths, the segment rule and the result block are engine.hip's
+// (declared in engine_state.hpp), as are the host-side objects (context, group, batch); of kernels.hpp this unit
+// instantiates count_kernel's SEG form and the device functions topk_kernels.hpp builds on.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -22,103 +21,39 @@
 #include "kwage_amd.h"
 #include "engine_state.hpp"
 #include "pool_blocks.hpp"
-
-namespace topk_dev {
 #include "kernels.hpp"
 #include "topk_kernels.hpp"
-}
-
-namespace dev = topk_dev::kwage;
 
 namespace kwage {
 namespace {
-
-// The batch's k-mer layout for k-mer length k: the one engine.hip built already, or built here and kept with the batch,
-// where later searches of either kind find it.  KEEP IN STEP WITH engine.hip batch_prepare: kwage_search uses a layout
-// built here without rebuilding it, so every field (position prefix, global-set offsets and sizes, the chunk work list,
-// max_pos / total_pos / table_slots) must come out exactly as batch_prepare computes it.
-int topk_layout(kwage_batch *b, uint32_t k, const KmerLayout **out)
-{
-	for(const auto &have : b->layouts){ if(have->k == k){ *out = have.get(); return KWAGE_OK; } }
-	std::unique_ptr<KmerLayout> L(new (std::nothrow) KmerLayout());
-	if(!L){ return fail(KWAGE_ERR_DEVICE, "out of host memory"); }
-	L->k = k;
-	const uint32_t n = b->n;
-	auto table_lg = [](uint64_t npos) { uint32_t lg = 6; while((1ull << lg) < 2*npos){ ++lg; } return lg; };
-	L->h_pos_off.assign((size_t)n + 1, 0);
-	std::vector<uint64_t> tab_off(n, 0);
-	std::vector<uint32_t> chunk_q;
-	std::vector<uint64_t> chunk_t0;
-	uint64_t slots = 0, maxp = 0;
-	for(uint32_t i = 0; i < n; ++i){
-		const uint64_t len = b->h_seq_off[i + 1] - b->h_seq_off[i];
-		const uint64_t npos = (len >= k) ? (len - k + 1) : 0;
-		L->h_pos_off[i + 1] = L->h_pos_off[i] + npos;
-		maxp = std::max(maxp, npos);
-		const bool is_long = npos && (1ull << table_lg(npos)) > dev::KM_LDS_SLOTS;      // global distinct set
-		if(is_long){ tab_off[i] = slots; slots += 1ull << table_lg(npos); }
-		if(!is_long || npos <= dev::KM_CHUNK){ chunk_q.push_back(i); chunk_t0.push_back(0); continue; }
-		L->multi_chunk = true;
-		for(uint64_t t0 = 0; t0 < npos; t0 += dev::KM_CHUNK){ chunk_q.push_back(i); chunk_t0.push_back(t0); }
-	}
-	if(chunk_q.size() > 0x7FFFFFFFull){ return fail(KWAGE_ERR_ARG, "batch too large for one k-mer launch"); }
-	L->n_chunks = chunk_q.size();
-	L->pool = &b->ctx->batch_pool;
-	HIP_TRY(L->pool->take(std::max<size_t>(chunk_q.size(), 1)*sizeof(uint32_t), (void**)&L->d_chunk_q, &L->cap_chunk_q));
-	HIP_TRY(L->pool->take(std::max<size_t>(chunk_q.size(), 1)*sizeof(uint64_t), (void**)&L->d_chunk_t0, &L->cap_chunk_t0));
-	HIP_TRY(L->pool->take(((size_t)n + 1)*sizeof(uint64_t), (void**)&L->d_pos_off, &L->cap_pos_off));
-	HIP_TRY(L->pool->take(std::max<size_t>(n, 1)*sizeof(uint64_t), (void**)&L->d_tab_off, &L->cap_tab_off));
-	hipStream_t us = b->ctx->upload_stream;
-	if(L->n_chunks){
-		HIP_TRY(hipMemcpyAsync(L->d_chunk_q, chunk_q.data(), chunk_q.size()*sizeof(uint32_t), hipMemcpyHostToDevice, us));
-		HIP_TRY(hipMemcpyAsync(L->d_chunk_t0, chunk_t0.data(), chunk_t0.size()*sizeof(uint64_t), hipMemcpyHostToDevice, us));
-	}
-	HIP_TRY(hipMemcpyAsync(L->d_pos_off, L->h_pos_off.data(), ((size_t)n + 1)*sizeof(uint64_t), hipMemcpyHostToDevice, us));
-	if(n){ HIP_TRY(hipMemcpyAsync(L->d_tab_off, tab_off.data(), (size_t)n*sizeof(uint64_t), hipMemcpyHostToDevice, us)); }
-	HIP_TRY(hipStreamSynchronize(us));
-	L->total_pos = L->h_pos_off[n];
-	L->max_pos = maxp;
-	L->table_slots = slots;
-	*out = L.get();
-	b->layouts.push_back(std::move(L));
-	return KWAGE_OK;
-}
 
 struct Events {
 	hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
 	~Events() { for(hipEvent_t e : ev){ if(e){ (void)hipEventDestroy(e); } } }
 };
 
-// counter planes for counts up to `max_count` (engine.hip planes_for: the instantiated sizes)
-uint32_t topk_planes_for(uint64_t max_count)
-{
-	uint32_t bits = 1;
-	while(bits < 32 && (max_count >> bits) != 0){ ++bits; }
-	return (bits <= 7) ? 7 : (bits <= 10) ? 10 : (bits <= 14) ? 14 : (bits <= 20) ? 20 : 32;
-}
-
 template <int PLANES, int NH>
-void launch_tile(const dev::SearchArgs &a, const dev::TopkArgs &t, hipStream_t s)
+void launch_tile(const SearchArgs &a, const TopkArgs &t, hipStream_t s)
 {
 	const uint64_t tiles = (uint64_t)a.n_queries*a.chunks;
-	hipLaunchKernelGGL((dev::topk_tile_kernel<PLANES, NH>), dim3((uint32_t)((tiles + 3)/4)), dim3(dev::SEARCH_THREADS), 0, s, a, t);
+	hipLaunchKernelGGL((topk_tile_kernel<PLANES, NH>), dim3((uint32_t)((tiles + 3)/4)), dim3(SEARCH_THREADS), 0, s, a, t);
 }
 
 template <int PLANES, int NH>
-void launch_seg_count(const dev::SearchArgs &a, hipStream_t s)
+void launch_seg_count(const SearchArgs &a, hipStream_t s)
 {
 	const uint64_t tiles = (uint64_t)a.n_queries*a.segs*a.chunks;
-	hipLaunchKernelGGL((dev::count_kernel<PLANES, NH, true>), dim3((uint32_t)((tiles + 3)/4)), dim3(dev::SEARCH_THREADS), 0, s, a);
+	hipLaunchKernelGGL((count_kernel<PLANES, NH, true>), dim3((uint32_t)((tiles + 3)/4)), dim3(SEARCH_THREADS), 0, s, a);
 }
 
 template <int PLANES>
-int launch_combine(const dev::SearchArgs &a, const dev::TopkArgs &t, uint32_t seg_planes, hipStream_t s)
+int launch_combine(const SearchArgs &a, const TopkArgs &t, uint32_t seg_planes, hipStream_t s)
 {
-	const size_t lds = (size_t)(dev::COMBINE_WAVES/2)*PLANES*dev::WAVE*16;
+	const size_t lds = (size_t)(COMBINE_WAVES/2)*PLANES*WAVE*16;
 	if(lds > 48*1024){
-		HIP_TRY(hipFuncSetAttribute((const void*)dev::topk_combine_kernel<PLANES>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+		HIP_TRY(hipFuncSetAttribute((const void*)topk_combine_kernel<PLANES>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
 	}
-	hipLaunchKernelGGL((dev::topk_combine_kernel<PLANES>), dim3(a.n_queries*a.chunks), dim3(dev::COMBINE_WAVES*dev::WAVE), lds, s, a, t, seg_planes);
+	hipLaunchKernelGGL((topk_combine_kernel<PLANES>), dim3(a.n_queries*a.chunks), dim3(COMBINE_WAVES*WAVE), lds, s, a, t, seg_planes);
 	return KWAGE_OK;
 }
 
@@ -144,42 +79,8 @@ void by_shape(uint32_t planes, uint32_t nh, A&&... args)
 		default: go(std::integral_constant<int, 32>()); break;
 	}
 }
-template <int P, int NH> struct TileLaunch { static void run(const dev::SearchArgs &a, const dev::TopkArgs &t, hipStream_t s) { launch_tile<P, NH>(a, t, s); } };
-template <int P, int NH> struct SegLaunch { static void run(const dev::SearchArgs &a, hipStream_t s) { launch_seg_count<P, NH>(a, s); } };
-
-// Segments of the k-mer lists (engine.hip choose_segments' rule): only while the launch has fewer than ~2048 waves,
-// never shorter than 64 k-mers, at most 1024; the tuning knob force_segs forces a count.
-void topk_segments(dev::SearchArgs &a, uint64_t max_kmers, int64_t force_segs)
-{
-	static const uint64_t TARGET_TILES = 2048, MIN_SEG_KMERS = 64, MAX_SEGS = 1024;
-	a.segs = 1;
-	a.seg_kmers = (uint32_t)std::max<uint64_t>(max_kmers, 1);
-	uint64_t want;
-	if(force_segs > 0){ want = (uint64_t)force_segs; }
-	else{
-		const uint64_t tiles = (uint64_t)a.n_queries*a.chunks;
-		if(tiles >= TARGET_TILES || max_kmers < 2*MIN_SEG_KMERS){ return; }
-		want = std::min<uint64_t>((TARGET_TILES + tiles - 1)/tiles, max_kmers/MIN_SEG_KMERS);
-	}
-	want = std::max<uint64_t>(1, std::min<uint64_t>(std::min(want, MAX_SEGS), std::max<uint64_t>(max_kmers, 1)));
-	if(want <= 1){ return; }
-	a.seg_kmers = (uint32_t)((max_kmers + want - 1)/want);
-	a.segs = (uint32_t)((max_kmers + a.seg_kmers - 1)/a.seg_kmers);
-}
-
-// KEEP IN STEP WITH engine.hip ResultStorage, member for member: kwage_result_free deletes every result through that
-// type, so a top-k result must have the same members in the same order (short lists only: `hits` owns the records,
-// the pool members stay empty and its destructor does nothing with them).  A change of ResultStorage must be mirrored
-// here; engine.hip is not edited by the change that adds this mode, so the coupling is stated on this side.
-struct TopkResultStorage {
-	kwage_result pub;
-	std::unique_ptr<kwage_hit[]> hits;
-	std::shared_ptr<PinnedPool> pool;
-	PinBuf pinned;
-	std::vector<uint32_t> nkmer, qthr;
-	char kernel[64];
-	~TopkResultStorage() { if(pool){ pool->release(pinned); } }
-};
+template <int P, int NH> struct TileLaunch { static void run(const SearchArgs &a, const TopkArgs &t, hipStream_t s) { launch_tile<P, NH>(a, t, s); } };
+template <int P, int NH> struct SegLaunch { static void run(const SearchArgs &a, hipStream_t s) { launch_seg_count<P, NH>(a, s); } };
 
 static const uint64_t CAND_BYTES_PER_SLICE = 256ull << 20;     // candidate keys of one slice of the batch's queries
 static const uint64_t SLAB_BYTES_PER_SLICE = 1ull << 30;       // partial counters of one slice (segmented form)
@@ -203,7 +104,7 @@ int topk_select(kwage_group *g, kwage_batch *b, uint32_t k, float threshold, uin
 	int rc;
 	if((rc = set_device(ctx))){ return rc; }
 	const KmerLayout *L = nullptr;
-	if((rc = topk_layout(b, g->params.kmer_len, &L))){ return rc; }
+	if((rc = batch_prepare(b, g->params.kmer_len, &L))){ return rc; }
 	const uint32_t nh = g->params.num_hash;
 	if(L->max_pos*nh > 0xFFFFFFFFull){
 		return fail(KWAGE_ERR_ARG, "a query of %llu k-mer positions x %u hash functions exceeds 2^32 rows", (unsigned long long)L->max_pos, nh);
@@ -232,43 +133,10 @@ int topk_select(kwage_group *g, kwage_batch *b, uint32_t k, float threshold, uin
 			if((rc = blocks.take(L->table_slots*sizeof(uint64_t), &d_tables))){ return rc; }
 			HIP_TRY(hipMemsetAsync(d_tables, 0xFF, L->table_slots*sizeof(uint64_t), s));
 		}
-		dev::KmerArgs ka;
-		ka.seqs = b->d_seqs;
-		ka.seq_off = b->d_seq_off;
-		ka.pos_off = L->d_pos_off;
-		ka.tab_off = L->d_tab_off;
-		ka.g_tables = d_tables;
-		ka.k = g->params.kmer_len;
-		ka.num_hash = nh;
-		ka.row_mask = (g->params.log_2_filter_len >= 32) ? 0xFFFFFFFFu : ((1u << g->params.log_2_filter_len) - 1u);
-		ka.threshold = threshold;
-		ka.complete_match = 0;          // the floor at t = 1 is n (kwage_search reports 0 there: its AND path has no floor)
-		ka.rows = d_rows;
-		ka.kmers_out = nullptr;
-		ka.nkmer = d_nkmer;
-		ka.qthr = d_qthr;
-		ka.total_kmers = nullptr;
-		ka.lds_slots = 64;
-		while(ka.lds_slots < dev::KM_LDS_SLOTS && ka.lds_slots < 2*L->max_pos){ ka.lds_slots *= 2; }
-		ka.shared_lg = 0;
-		ka.bloom_bits = nullptr;
-		ka.chunk_q = L->d_chunk_q;
-		ka.chunk_t0 = L->d_chunk_t0;
-		if(L->multi_chunk){ HIP_TRY(hipMemsetAsync(d_nkmer, 0, (size_t)n*sizeof(uint32_t), s)); }
-		const uint32_t threads = (L->max_pos <= 192) ? 64 : (L->max_pos <= 768) ? 128 : dev::KM_THREADS;
-		hipLaunchKernelGGL(dev::kmer_kernel, dim3((uint32_t)L->n_chunks), dim3(threads), (size_t)ka.lds_slots*sizeof(uint64_t), s, ka);
-		HIP_TRY(hipGetLastError());
-		if(L->multi_chunk){
-			hipLaunchKernelGGL(dev::kmer_finish_kernel, dim3((n + 255)/256), dim3(256), 0, s, ka, n);
-			HIP_TRY(hipGetLastError());
-		}
-		if(g->d_row_map){      // sparse group: row index -> position in the group's row list
-			const uint64_t per_q = std::max<uint64_t>(1, (L->max_pos*nh + 4095)/4096);
-			const uint64_t wgs_per_q = std::min<uint64_t>(per_q, std::max<uint64_t>(1, 0x7FFFFFFFull/n));
-			hipLaunchKernelGGL(dev::remap_rows_kernel, dim3((uint32_t)(n*wgs_per_q)), dim3(256), 0, s, d_rows, L->d_pos_off, d_nkmer,
-			                   nh, g->d_row_map, (uint32_t)g->h_row_map.size(), d_missing, (uint32_t)wgs_per_q);
-			HIP_TRY(hipGetLastError());
-		}
+		// (the floor at t = 1 is n: no complete_match here.  kwage_search reports 0 there, its AND path has no floor)
+		const KmerStageOut o = {d_rows, nullptr, d_nkmer, d_qthr, d_tables};
+		if((rc = launch_kmer_kernels(g->params, b, L, threshold, 0, o, s))){ return rc; }
+		if(g->d_row_map && (rc = launch_remap_rows(g, n, L, d_rows, d_nkmer, d_missing, s))){ return rc; }
 	}
 	if(timing_kmer){ HIP_TRY(hipEventRecord(ev.ev[1], s)); }
 
@@ -277,7 +145,7 @@ int topk_select(kwage_group *g, kwage_batch *b, uint32_t k, float threshold, uin
 	uint32_t launches = 0;
 	if(timing){ HIP_TRY(hipEventRecord(ev.ev[2], s)); }
 	if(n && g->num_columns){
-		dev::SearchArgs a;
+		SearchArgs a;
 		memset(&a, 0, sizeof(a));
 		a.db = g->d_bits;
 		a.stride = g->stride;
@@ -285,19 +153,19 @@ int topk_select(kwage_group *g, kwage_batch *b, uint32_t k, float threshold, uin
 		a.valid = g->d_valid;
 		a.rows = d_rows;
 		a.num_hash = nh;
-		a.chunks = (a.units_per_row + dev::WAVE - 1)/dev::WAVE;
-		const uint32_t planes = topk_planes_for(L->max_pos);
+		a.chunks = (a.units_per_row + WAVE - 1)/WAVE;
+		const uint32_t planes = planes_for(L->max_pos);
 		const uint64_t cand_per_q = (uint64_t)a.chunks*k*sizeof(unsigned long long);
 		uint32_t slice = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(n, CAND_BYTES_PER_SLICE/cand_per_q));
 		a.n_queries = slice;
-		topk_segments(a, L->max_pos, ctx->tune.force_segs);
-		uint32_t seg_planes = (a.segs > 1) ? topk_planes_for(a.seg_kmers) : planes;
+		choose_segments(a, L->max_pos, 1024, ctx->tune.force_segs);      // (topk_combine_kernel's grid is flat: any number of queries)
+		uint32_t seg_planes = (a.segs > 1) ? planes_for(a.seg_kmers) : planes;
 		if(a.segs > 1){      // keep the slab of partial counters bounded: fewer queries per slice
 			const uint64_t slab_per_q = (uint64_t)a.segs*seg_planes*g->stride;
 			slice = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(slice, SLAB_BYTES_PER_SLICE/slab_per_q));
 		}
 		if((uint64_t)slice*a.segs*a.chunks/4 + 1 > 0x7FFFFFFFull){ return fail(KWAGE_ERR_ARG, "batch too large for one launch"); }
-		dev::TopkArgs t;
+		TopkArgs t;
 		t.k = k;
 		t.tiles = a.chunks;
 		if((rc = blocks.take((uint64_t)slice*cand_per_q, &t.cand))){ return rc; }
@@ -332,7 +200,7 @@ int topk_select(kwage_group *g, kwage_batch *b, uint32_t k, float threshold, uin
 				by_shape<TileLaunch>(planes, nh, a, t, s);
 			}
 			HIP_TRY(hipGetLastError());
-			hipLaunchKernelGGL(dev::topk_merge_kernel, dim3(a.n_queries), dim3(dev::MERGE_THREADS), 0, s, t, q0, d_out + (uint64_t)q0*k, d_out_n + q0);
+			hipLaunchKernelGGL(topk_merge_kernel, dim3(a.n_queries), dim3(MERGE_THREADS), 0, s, t, q0, d_out + (uint64_t)q0*k, d_out_n + q0);
 			HIP_TRY(hipGetLastError());
 			++launches;
 		}
@@ -376,7 +244,7 @@ int search_topk(kwage_group *g, kwage_batch *b, uint32_t k, float threshold, uin
 	const uint32_t launches = sel.launches;
 
 	// ---- copy back: per-query arrays, missing-row counter, the <= k records per query -----------------------------------
-	std::unique_ptr<TopkResultStorage> rs(new (std::nothrow) TopkResultStorage());
+	std::unique_ptr<ResultStorage> rs(new (std::nothrow) ResultStorage());
 	if(!rs){ return fail(KWAGE_ERR_DEVICE, "out of host memory"); }
 	rs->nkmer.assign(n, 0);
 	rs->qthr.assign(n, 0);
@@ -458,7 +326,7 @@ int search_topk_device_append(kwage_group *g, kwage_batch *b, uint32_t k, float 
 		unsigned long long *d_off = nullptr;
 		if((rc = blocks.take((uint64_t)n*sizeof(unsigned long long), &d_off))){ return rc; }
 		HIP_TRY(hipMemcpyAsync(d_off, off.data(), (size_t)n*sizeof(unsigned long long), hipMemcpyHostToDevice, s));
-		hipLaunchKernelGGL(dev::topk_append_kernel, dim3(n), dim3(dev::WAVE), 0, s, sel.d_out, sel.d_out_n, k, d_off, base,
+		hipLaunchKernelGGL(topk_append_kernel, dim3(n), dim3(WAVE), 0, s, sel.d_out, sel.d_out_n, k, d_off, base,
 		                   column_base, (kwage_hit*)hits_dev, (unsigned long long)capacity);
 		HIP_TRY(hipGetLastError());
 	}

@@ -1,7 +1,7 @@
 // kwage_amd/csrc/topk_kernels.hpp -- gfx950 kernels of the top-k search (kwage_search_topk): for every query the k
-// columns with the highest counts, selected on the device.  Included by topk.hip only, AFTER kernels.hpp and inside
-// the same enclosing namespace (topk.hip explains why): the counting loop, the tile decomposition and the bit-sliced
-// comparator are kernels.hpp's own (count_kmers, planes_ge, planes_accumulate, count_kernel's SEG form).
+// columns with the highest counts, selected on the device.  Included by topk.hip only, AFTER kernels.hpp: the counting
+// loop, the tile decomposition and the bit-sliced comparator are kernels.hpp's own (count_kmers, planes_ge,
+// planes_accumulate, count_kernel's SEG form).
 //
 //   topk_tile_kernel     count_kernel's tile loop (one wave = one query x 64 units of 16 B = 8192 columns), then a
 //                        per-tile selection in place of emit_count_hits: the tile's best <= k columns go to the
