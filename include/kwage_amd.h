@@ -278,6 +278,31 @@ int kwage_topk_merge_device(kwage_ctx *ctx, const void *hits_dev, uint64_t n_hit
                             const void *order_dev, uint64_t n_order, void *out_dev, uint64_t out_capacity,
                             void *out_count_dev);
 
+/* Dense score search, no counterpart in the reference: cell (q, c) = the num_match kwage_search would report for
+ * column c and query q at a threshold whose floor is 0; 0 for pad columns (never counted) and for a query without k-mers.
+ *   - cells are uint32; cell (q, c) lies at scores[q*row_elems + c] for c in [0, kwage_group_column_span(g)); cells at
+ *     or beyond the span in a row are not touched;
+ *   - row_elems >= the span and row_elems % 4 == 0; scores_dev is 16-byte aligned.  Spans and the column bases of
+ *     groups are multiples of 8 columns, so a caller places several groups side by side in one matrix by offsetting
+ *     the pointer;
+ *   - num_query_kmer / num_query_kmer_dev may be NULL or hold n_queries uint32 (host / device memory);
+ *   - KWAGE_SEARCH_TIMING fills *search_kernel_ms (may be NULL) with the HIP-event duration of the score kernels;
+ *     KWAGE_SEARCH_EARLY_EXIT is ignored: every column is counted to the end.
+ * Errors of two kinds.  Found on the host before any kernel is launched: KWAGE_ERR_STATE before kwage_group_finalize;
+ * KWAGE_ERR_ARG for mixed contexts, a wrong row_elems, a misaligned or NULL pointer, a query of 2^32 rows and more, or
+ * a batch too large for one launch.  Found on the device: KWAGE_ERR_STATE for a sparse group whose row list does not
+ * cover the batch, which is known only once the k-mer stage has computed the batch's rows; a search of a sparse group
+ * waits for that answer (one 8-byte copy) before it launches the score kernels, so in either kind no cell is written.
+ * Synchronous; runs on the context's first stream; device scratch comes from the context's pool.  kwage_search_scores
+ * is the same search with the matrix copied to host memory. */
+int kwage_search_scores_device(kwage_group *g, kwage_batch *b, void *scores_dev, uint64_t row_elems,
+                               void *num_query_kmer_dev, uint32_t flags, float *search_kernel_ms);
+int kwage_search_scores(kwage_group *g, kwage_batch *b, uint32_t *scores, uint64_t row_elems,
+                        uint32_t *num_query_kmer, uint32_t flags, float *search_kernel_ms);
+/* Which kernels the calling thread's last dense score search launched, with their template shapes:
+ * "score_tile_kernel<10,1>", "count_kernel<7,1>+score_combine_kernel<14>"; "" if none.  Valid until the thread's next one. */
+const char *kwage_search_scores_kernel(void);
+
 /* The same search in two halves, for hosts that stream many batches: submit enqueues the whole device
  * pipeline and returns at once; collect waits for it and builds the result.  A context holds at most TWO
  * pending searches (each on its own HIP stream), so the k-mer stage, copy-back and host post-processing

@@ -6,6 +6,7 @@
 //   loader.hip   database groups: allocation, the loaders (.db files raw and compressed, sparse groups), synthetic columns
 //   topk.hip     the top-k search: engine.hip's batch layout, k-mer stage, counter widths, segment rule and result block
 //                (declared at the end of this file), then its own selection kernels
+//   scores.hip   the dense score search: the same shared stages, then its own expand-and-store kernels
 #ifndef KWAGE_AMD_ENGINE_STATE_HPP
 #define KWAGE_AMD_ENGINE_STATE_HPP
 
@@ -297,6 +298,8 @@ struct Tuning {
 	int64_t and_wide = 1;           // KWAGE_AND_WIDE: rows beyond the walk form's range, no early exit, a chip-filling launch: vec 4, 8 rows, 8 waves per CU (and_config)
 	int64_t narrow = 1;             // KWAGE_NARROW: several queries per wave for rows <= 512 B
 	int64_t force_segs = 0;         // KWAGE_FORCE_SEGS: cut every query's k-mer list into this many segments (tests)
+	int64_t scores_form = 0;        // KWAGE_SCORES_FORM: the dense score search's store epilogue (scores_kernels.hpp): 0 = a KiB of consecutive cells per store
+	                                //   instruction, the planes crossing lanes through LDS; 1 = every lane stores its own 512-byte run (at C2 the first is the faster by just under 1 %: profiles/r06_scores_bench.txt)
 	int64_t ee_refine = 1;          // KWAGE_EE_REFINE: with early exit, tiles that still hold a candidate column after the first rows are handed over to the
 	                                //   refine launch, which reads 128-byte groups on a balanced grid (0: the tile's own wave walks on 1-2 KiB wide)
 	int64_t refine_seg_rows = 32;   // KWAGE_REFINE_SEG_ROWS: rows (k-mers at t < 1) per unit of the refine launch (t < 1: at most 120).  32: four units for what is left of a 150-base read

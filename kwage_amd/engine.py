@@ -295,9 +295,13 @@ def search_topk(group: Group, batch: Batch, k: int, threshold: float = 0.0, flag
     return _unpack_result(res)
 
 
-def _device_tensor(t, name: str, dtype, cols: int = 0):
+def _device_tensor(t, name: str, dtype, cols: int = 0, row_multiple: int = 0):
+    """row_multiple > 0: a 2-D tensor whose rows are contiguous and lie a multiple of that many elements apart (a block of
+    columns of a wider matrix) is accepted as well."""
     import torch
-    if not isinstance(t, torch.Tensor) or t.device.type != "cuda" or t.dtype != dtype or not t.is_contiguous():
+    strided_rows = (row_multiple > 0 and isinstance(t, torch.Tensor) and t.dim() == 2 and (t.shape[1] <= 1 or t.stride(1) == 1)
+                    and (t.shape[0] <= 1 or (t.stride(0) >= t.shape[1] and t.stride(0) % row_multiple == 0)))
+    if not isinstance(t, torch.Tensor) or t.device.type != "cuda" or t.dtype != dtype or not (t.is_contiguous() or strided_rows):
         raise ValueError("%s: a contiguous %s tensor on a device is required" % (name, dtype))
     if cols and (t.dim() != 2 or t.shape[1] != cols):
         raise ValueError("%s: shape [n, %d] required, got %s" % (name, cols, tuple(t.shape)))
@@ -343,6 +347,45 @@ def merge_topk_device(ctx: Context, hits, n_queries: int, k: int, order=None):
     return out[:int(count.item())]
 
 
+@dataclass
+class ScoreResult:
+    scores: object                   # uint32 [n, span] numpy array (search_scores) / the caller's device tensor (search_scores_device)
+    num_query_kmer: object           # uint32 per query, or None (search_scores_device without the tensor)
+    kernel: str                      # "score_tile_kernel<10,1>", "count_kernel<7,1>+score_combine_kernel<14>", "" if nothing ran
+    kernel_ms: float                 # with SEARCH_TIMING, else 0
+
+
+def search_scores(group: Group, batch: Batch, flags: int = 0) -> ScoreResult:
+    """kwage_search_scores(): the num_match of every column of the group for every query, as a uint32 [n, column_span]
+    matrix (pad columns and queries without k-mers: 0)."""
+    n, span = batch.n, group.column_span
+    scores = np.zeros((n, span), dtype=np.uint32)
+    nk = np.zeros(max(n, 1), dtype=np.uint32)
+    ms = C.c_float(0)
+    check(lib().kwage_search_scores(group._h, batch._h, scores.ctypes.data if scores.size else None, span, nk.ctypes.data, flags, C.byref(ms)))
+    return ScoreResult(scores, nk[:n], (lib().kwage_search_scores_kernel() or b"").decode(), float(ms.value))
+
+
+def search_scores_device(group: Group, batch: Batch, out, num_query_kmer=None, flags: int = 0) -> ScoreResult:
+    """kwage_search_scores_device(): the same matrix written into `out`, an int32 device tensor [n, >= column_span] with
+    unit inner stride and rows a multiple of 4 elements apart (a block of columns of a wider matrix will do); columns of
+    `out` at or beyond the group's span are left alone.  num_query_kmer: None or an int32 [n] device tensor."""
+    import torch
+    _device_tensor(out, "out", torch.int32, row_multiple=4)
+    span = group.column_span
+    if out.dim() != 2 or out.shape[0] != batch.n or out.shape[1] < span:
+        raise ValueError("out: shape [%d, >= %d] required, got %s" % (batch.n, span, tuple(out.shape)))
+    row_elems = out.stride(0) if out.shape[0] > 1 else span      # (a single row: the distance between rows addresses nothing)
+    nk = 0
+    if num_query_kmer is not None:
+        if _device_tensor(num_query_kmer, "num_query_kmer", torch.int32).numel() < batch.n:
+            raise ValueError("num_query_kmer: %d elements required" % batch.n)
+        nk = num_query_kmer.data_ptr()
+    ms = C.c_float(0)
+    check(lib().kwage_search_scores_device(group._h, batch._h, out.data_ptr() or None, row_elems, nk or None, flags, C.byref(ms)))
+    return ScoreResult(out, num_query_kmer, (lib().kwage_search_scores_kernel() or b"").decode(), float(ms.value))
+
+
 class PendingSearch:
     """A submitted search (kwage_search_submit); collect() waits for it and returns the result."""
 
@@ -369,6 +412,7 @@ def submit(group: Group, batch: Batch, threshold: float, flags: int = 0) -> Pend
 Group.search = lambda self, batch, threshold, flags=0: search(self, batch, threshold, flags)
 Group.search_topk = lambda self, batch, k, threshold=0.0, flags=0: search_topk(self, batch, k, threshold, flags)
 Group.submit = lambda self, batch, threshold, flags=0: submit(self, batch, threshold, flags)
+Group.search_scores = lambda self, batch, flags=0: search_scores(self, batch, flags)
 
 
 def hash_batch(ctx: Context, kmer_len: int, num_hash: int, log_2_filter_len: int, batch: Batch
@@ -440,6 +484,24 @@ class Database:
             out[q].append((gi, c - bases[gi], m))
         for lst in out:
             lst.sort(key=lambda h: (-h[2], h[0], h[1]))
+        return out
+
+    def search_scores(self, batch: Batch):
+        """Every query's score for every column of the whole database: one int32 device tensor [n, sum of the groups'
+        column spans] in a single allocation, each group's block at the column base Database.search_topk gives it
+        (groups in order); pad columns hold 0."""
+        import torch
+        if not self.groups:
+            raise ValueError("Database.search_scores: no groups")
+        dev = torch.device("cuda", self.groups[0].ctx.device)
+        bases, at = [], 0
+        for g in self.groups:
+            bases.append(at)
+            at += g.column_span
+        out = torch.empty((batch.n, at), dtype=torch.int32, device=dev)
+        for g, base in zip(self.groups, bases):
+            if batch.n and g.column_span:
+                search_scores_device(g, batch, out[:, base:base + g.column_span])
         return out
 
     def close(self) -> None:
@@ -549,6 +611,24 @@ class FileDatabase(Database):
             best = sorted(per_query[q], key=lambda h: (-h[0], order[h[1]], h[2]))[:k]
             out.extend(DatabaseHit(q, path, col, self._accession(path, col), m, nk) for m, path, col, nk in best)
         return out
+
+    def score_matrix(self, seqs: Sequence[bytes | str]) -> Tuple[np.ndarray, List[str]]:
+        """What `kwage_scores -d ... <seqs>` prints, as (uint32 [n_queries, n_samples], run accessions): the real columns
+        only, in file order then column order."""
+        where = {path: (base, first, nf) for base, layout in zip(np.cumsum([0] + [g.column_span for g in self.groups]), self._layout)
+                 for first, nf, path in layout}
+        cols, accessions = [], []
+        for f in self.files:
+            base, first, nf = where[f]
+            cols.append(int(base) + first + np.arange(nf, dtype=np.int64))
+            accessions.extend(self._accession(f, c) for c in range(nf))
+        cols = np.concatenate(cols) if cols else np.zeros(0, np.int64)
+        b = Batch(self.ctx, seqs)
+        try:
+            full = self.search_scores(b).cpu().numpy().view(np.uint32) if self.groups else np.zeros((b.n, 0), np.uint32)
+        finally:
+            b.close()
+        return np.ascontiguousarray(full[:, cols]), accessions
 
     def close(self) -> None:
         for d in self._info.values():

@@ -247,9 +247,14 @@ def rounds():
     return sorted({m.group(1) for p in glob.glob(os.path.join(PROF, "r[0-9][0-9]_*")) for m in [re.match(r"(r\d\d)_", os.path.basename(p))] if m}, reverse=True)
 
 
+def bench_rounds():
+    """The rounds that filed `bench.py` lines (a round may consist of records of other tools only: no tables of it here)."""
+    return [rnd for rnd in rounds() if bench_rows(rnd)]
+
+
 def render_tables():
     out = ["# profiles/TABLES.md — generated by `tools/render_tables.py` from the files in this directory; do not edit", ""]
-    for rnd in rounds():
+    for rnd in bench_rounds():
         out += ["## Round %s — `bench.py` lines (`%s_*.json`)" % (rnd[1:].lstrip("0"), rnd), ""] + bench_table(rnd) + [""]
         et = early_exit_table(rnd)
         if len(et) > 2:
@@ -277,8 +282,8 @@ DESIGN_END = "<!-- GENERATED:measurements END -->"
 
 
 def design_block():
-    """The newest round's tables as DESIGN.md carries them between its markers."""
-    rnd = rounds()[0]
+    """The tables of the newest round with `bench.py` lines, as DESIGN.md carries them between its markers."""
+    rnd = bench_rounds()[0]
     block = ["", "`bench.py` lines of round %s (`profiles/%s_*.json`):" % (rnd[1:].lstrip("0"), rnd), ""] + bench_table(rnd)
     et = early_exit_table(rnd)
     if len(et) > 2:
