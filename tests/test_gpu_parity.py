@@ -47,6 +47,10 @@ def test_kmer_stage_golden_vectors(ka, ctx, oracle):
 
 @pytest.mark.parametrize("k", [1, 2, 3, 4, 5, 8, 15, 16, 17, 21, 27, 28, 29, 30, 31, 32])
 def test_kmer_stage_vs_oracle(ka, ctx, oracle, k):
+    """Every k-mer length, in ONE launch form: the 30 000-base query sizes the launch, so every query here runs in 256-thread
+    workgroups with a 4096-slot LDS table (num_hash = 3, L = 20).  The 64- and 128-thread workgroups, the smaller tables,
+    the edges between the forms, the other hash counts and filter lengths, the float32 floor and what one launch leaves to
+    the next: tests/test_gpu_kmer_shapes.py (its table: tests/kmer_shapes.py)."""
     rng = np.random.default_rng(1000 + k)
     seqs = ["", "A", "ACGT" * 3, "N" * 50, rand_seq(rng, 31), rand_seq(rng, 32), rand_seq(rng, 33),
             rand_seq(rng, 150), rand_seq(rng, 150).lower(), rand_seq(rng, 1000),
