@@ -303,6 +303,64 @@ int kwage_search_scores(kwage_group *g, kwage_batch *b, uint32_t *scores, uint64
  * "score_tile_kernel<10,1>", "count_kernel<7,1>+score_combine_kernel<14>"; "" if none.  Valid until the thread's next one. */
 const char *kwage_search_scores_kernel(void);
 
+/* Filter set, no counterpart in the reference: n whole Bloom filters over 2^L rows as the QUESTIONS of a search ("which
+ * samples look like this sample").  On the device a set is one concatenated uint32 row list -- the rows in which each
+ * filter is set, ascending -- with a uint64 prefix array of n + 1 entries and each filter's set-bit count: the shape a
+ * batch's row indices have after the k-mer stage.  A set belongs to its context and carries the kwage_params it was
+ * made with; its device memory comes from and returns to the context's pool, so it is destroyed before the context.
+ *   - from_columns: `columns` are global column numbers of a finalized, non-sparse group (the same column may be named
+ *     twice).  KWAGE_ERR_STATE before kwage_group_finalize; KWAGE_ERR_ARG for a column at or beyond the span, a pad
+ *     column, a sparse group.
+ *   - from_bits: `bits` holds n host bit vectors of 2^L bits each, LSB first (the payload order of a `.bloom` file,
+ *     what kwage_bloom_bits_from_batch writes), filter_stride_bytes apart (ignored when n < 2).  For L < 3 a filter
+ *     is the low 2^L bits of one byte; higher bits are ignored.
+ *   - both: L = 32 is refused (KWAGE_ERR_ARG: a full filter's count does not fit 32 bits), as is a set too large for
+ *     one launch; n = 0 gives a valid empty set; a row list that cannot be allocated returns the pool's error.  On
+ *     any error *out is not written.
+ * Synchronous; runs on the context's first stream. */
+typedef struct kwage_filterset kwage_filterset;
+int kwage_filterset_from_columns(kwage_group *g, const uint64_t *columns, uint32_t n, kwage_filterset **out);
+int kwage_filterset_from_bits(kwage_ctx *ctx, const kwage_params *params, const void *bits, uint64_t filter_stride_bytes,
+                              uint32_t n, kwage_filterset **out);
+void kwage_filterset_destroy(kwage_filterset *fs);
+uint32_t kwage_filterset_num_filters(const kwage_filterset *fs);
+/* Every filter's set-bit count (n uint32). */
+int kwage_filterset_bit_counts(const kwage_filterset *fs, uint32_t *out);
+/* Diagnostic: the first min(capacity, count) rows of filter i copied from the device; *count = the filter's set-bit
+ * count.  Nothing on a search path calls it. */
+int kwage_filterset_read_rows(const kwage_filterset *fs, uint32_t i, uint32_t *out, uint64_t capacity, uint64_t *count);
+
+/* Filter search: cell (i, c) = the number of rows set in both filter i of the set and column c of the group; 0 for pad
+ * columns and for an empty filter.
+ *   - cells are uint32; cell (i, c) lies at scores[i*row_elems + c] for c in [0, kwage_group_column_span(g)); cells at
+ *     or beyond the span in a row are not touched;
+ *   - row_elems >= the span and row_elems % 4 == 0; scores_dev is 16-byte aligned.  Spans and the column bases of
+ *     groups are multiples of 8 columns, so a caller places several groups side by side in one matrix by offsetting
+ *     the pointer;
+ *   - KWAGE_SEARCH_TIMING fills *search_kernel_ms (may be NULL) with the HIP-event duration of the score kernels;
+ *     KWAGE_SEARCH_EARLY_EXIT is ignored: every column is counted to the end.
+ * A set made from one group's columns searches any group of the same context with the same parameters.  Errors, all
+ * found on the host before any kernel is launched: KWAGE_ERR_STATE before kwage_group_finalize; KWAGE_ERR_ARG when the
+ * group's kmer_len, num_hash, log_2_filter_len or hash_func differ from the set's (filters built differently are not
+ * comparable), for a sparse group, mixed contexts, a wrong row_elems, a misaligned or NULL pointer, or a set too large
+ * for one launch.  The kernels are the dense score search's own, in their one-hash-function instantiations, over one row
+ * per list entry.  Synchronous; runs on the context's first stream; device scratch comes from the context's pool.
+ * The second form is the same search with the matrix copied to host memory. */
+int kwage_search_filter_scores_device(kwage_group *g, kwage_filterset *fs, void *scores_dev, uint64_t row_elems,
+                                      uint32_t flags, float *search_kernel_ms);
+int kwage_search_filter_scores(kwage_group *g, kwage_filterset *fs, uint32_t *scores, uint64_t row_elems,
+                               uint32_t flags, float *search_kernel_ms);
+/* Which kernels the calling thread's last filter search launched: "score_tile_kernel<10,1>",
+ * "count_kernel<7,1>+score_combine_kernel<14>"; "" if none.  Valid until the thread's next one. */
+const char *kwage_search_filter_kernel(void);
+
+/* The set-bit count of every column of a finalized, non-sparse group (the denominator of a Jaccard index): span uint32
+ * cells, 0 on pad columns; the device form wants a 16-byte aligned pointer.  It is the filter search with one full
+ * filter, whose row list 0, 1, .. 2^L - 1 is built on the device: KWAGE_ERR_ARG for L = 32 and for a sparse group,
+ * KWAGE_ERR_STATE before finalize, KWAGE_ERR_DEVICE naming the row list when its 2^L x 4 bytes cannot be allocated. */
+int kwage_group_column_bits(kwage_group *g, uint32_t *out);
+int kwage_group_column_bits_device(kwage_group *g, void *out_dev);
+
 /* The same search in two halves, for hosts that stream many batches: submit enqueues the whole device
  * pipeline and returns at once; collect waits for it and builds the result.  A context holds at most TWO
  * pending searches (each on its own HIP stream), so the k-mer stage, copy-back and host post-processing

@@ -6,7 +6,8 @@
 //   loader.hip   database groups: allocation, the loaders (.db files raw and compressed, sparse groups), synthetic columns
 //   topk.hip     the top-k search: engine.hip's batch layout, k-mer stage, counter widths, segment rule and result block
 //                (declared at the end of this file), then its own selection kernels
-//   scores.hip   the dense score search: the same shared stages, then its own expand-and-store kernels
+//   scores.hip   the dense score search: the same shared stages, then its own expand-and-store kernels (score_stage.hpp)
+//   filterset.hip  filter sets (row lists made from whole Bloom filters) and the filter search, which runs scores.hip's stage
 #ifndef KWAGE_AMD_ENGINE_STATE_HPP
 #define KWAGE_AMD_ENGINE_STATE_HPP
 

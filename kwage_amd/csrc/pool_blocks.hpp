@@ -1,5 +1,5 @@
 // kwage_amd/csrc/pool_blocks.hpp -- device blocks of one synchronous call, taken from the context's batch pool and
-// handed back when the call ends.  Shared by topk.hip and topk_merge.hip.  The caller synchronises the stream before
+// handed back when the call ends.  Shared by topk.hip, topk_merge.hip, scores.hip and filterset.hip.  The caller synchronises the stream before
 // the object goes out of scope on an error path: nothing queued by the call may still read the blocks.
 #ifndef KWAGE_AMD_POOL_BLOCKS_HPP
 #define KWAGE_AMD_POOL_BLOCKS_HPP

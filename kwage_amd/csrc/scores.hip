@@ -9,6 +9,9 @@
 // engine_state.hpp), as are the host-side objects (context, group, batch); of kernels.hpp this unit instantiates
 // count_kernel's SEG form and the device functions scores_kernels.hpp builds on.  No hit list, no atomic, no sort:
 // each call writes queries x span x 4 bytes.
+//
+// The score stage (score_stage.hpp: score_stage_plan, score_stage_run) takes a row-list view, not a batch: the filter
+// search (filterset.hip) runs it over row lists that no k-mer stage made.  Every score kernel lives here.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -21,6 +24,7 @@
 #include "kwage_amd.h"
 #include "engine_state.hpp"
 #include "pool_blocks.hpp"
+#include "score_stage.hpp"
 #include "kernels.hpp"
 #include "scores_kernels.hpp"
 
@@ -100,6 +104,113 @@ int scores_check(kwage_group *g, kwage_batch *b, uint64_t row_elems, const char 
 	return KWAGE_OK;
 }
 
+}  // namespace
+
+// The launches' shapes, planned (and refused) before the first kernel.
+int score_stage_plan(const kwage_group *g, uint32_t n, uint64_t max_count, ScorePlan *plan)
+{
+	kwage_ctx *ctx = g->ctx;
+	const uint64_t span = g->next_byte*8;
+	SearchArgs a;
+	memset(&a, 0, sizeof(a));
+	a.units_per_row = (uint32_t)(g->stride/16);
+	a.chunks = (a.units_per_row + WAVE - 1)/WAVE;
+	if((uint64_t)n*a.chunks > 0xFFFFFFFFull){ return fail(KWAGE_ERR_ARG, "batch too large for one launch"); }
+	uint32_t planes = 0, seg_planes = 0, slice = n;
+	if(n && span){
+		planes = planes_for(max_count);
+		a.n_queries = n;
+		choose_segments(a, max_count, 1024, ctx->tune.force_segs);
+		seg_planes = (a.segs > 1) ? planes_for(a.seg_kmers) : planes;
+		if(a.segs > 1){      // keep the slab of partial counters bounded: fewer queries per slice
+			const uint64_t slab_per_q = (uint64_t)a.segs*seg_planes*g->stride;
+			slice = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(slice, SLAB_BYTES_PER_SLICE/slab_per_q));
+			// score_combine_kernel's grid is one workgroup per (query, tile): a slice's threads stay below 2^32
+			const uint64_t max_wgs = 0xFFFFFFFFull/(COMBINE_WAVES*WAVE);
+			if(a.chunks > max_wgs){ return fail(KWAGE_ERR_ARG, "batch too large for one launch"); }
+			slice = (uint32_t)std::min<uint64_t>(slice, max_wgs/a.chunks);
+		}
+		if((uint64_t)slice*a.segs*a.chunks/4 + 1 > 0x7FFFFFFFull){ return fail(KWAGE_ERR_ARG, "batch too large for one launch"); }
+	}
+	plan->units_per_row = a.units_per_row;
+	plan->chunks = a.chunks;
+	plan->planes = planes;
+	plan->seg_planes = seg_planes;
+	plan->segs = a.segs;
+	plan->seg_kmers = a.seg_kmers;
+	plan->slice = slice;
+	return KWAGE_OK;
+}
+
+// ---- scores: tile kernels, or segments + combine slice by slice of the queries ---------------------------------------
+int score_stage_run(kwage_group *g, const RowListView &v, const ScorePlan &plan, ScoreArgs sa, uint32_t flags, float *ms,
+                    PoolBlocks &blocks, char *kernel_name)
+{
+	int rc;
+	kwage_ctx *ctx = g->ctx;
+	hipStream_t s = ctx->stream;
+	const uint32_t n = v.n, nh = v.num_hash;
+	const uint64_t span = g->next_byte*8;
+	const bool timing = (flags & KWAGE_SEARCH_TIMING) != 0 && ms;
+	Events ev;
+	if(timing){ for(hipEvent_t &e : ev.ev){ HIP_TRY(hipEventCreate(&e)); } }
+	if(timing){ HIP_TRY(hipEventRecord(ev.ev[0], s)); }
+	if(n && span){
+		SearchArgs a;
+		memset(&a, 0, sizeof(a));
+		a.units_per_row = plan.units_per_row;
+		a.chunks = plan.chunks;
+		a.segs = plan.segs;
+		a.seg_kmers = plan.seg_kmers;
+		a.db = g->d_bits;
+		a.stride = g->stride;
+		a.valid = g->d_valid;
+		a.rows = v.rows;
+		a.num_hash = nh;
+		const uint32_t planes = plan.planes, seg_planes = plan.seg_planes, slice = plan.slice;
+		uint32_t *const out0 = sa.out;
+		sa.span = span;
+		sa.form = (ctx->tune.scores_form == (int64_t)SCORES_FORM_LANE) ? SCORES_FORM_LANE : SCORES_FORM_WAVE;
+		if(a.segs > 1){
+			uint32_t *slab = nullptr;
+			if((rc = blocks.take((uint64_t)slice*a.segs*seg_planes*g->stride, &slab))){ return rc; }
+			a.partial = slab;
+			snprintf(kernel_name, 64, "count_kernel<%u,%u>+score_combine_kernel<%u>", seg_planes, std::min(nh, 5u), planes);
+		}
+		else{
+			snprintf(kernel_name, 64, "score_tile_kernel<%u,%u>", planes, std::min(nh, 5u));
+		}
+		for(uint32_t q0 = 0; q0 < n; q0 += slice){
+			a.n_queries = std::min(slice, n - q0);
+			a.pos_off = v.pos_off + q0;
+			a.nkmer = v.counts + q0;
+			sa.out = out0 + (uint64_t)q0*sa.row_elems;
+			if(a.segs > 1){
+				by_shape<SegLaunch>(seg_planes, nh, a, s);
+				HIP_TRY(hipGetLastError());
+				switch(planes){
+					case 7: rc = launch_combine<7>(a, sa, seg_planes, s); break;
+					case 10: rc = launch_combine<10>(a, sa, seg_planes, s); break;
+					case 14: rc = launch_combine<14>(a, sa, seg_planes, s); break;
+					case 20: rc = launch_combine<20>(a, sa, seg_planes, s); break;
+					default: rc = launch_combine<32>(a, sa, seg_planes, s); break;
+				}
+				if(rc){ return rc; }
+			}
+			else{
+				by_shape<TileLaunch>(planes, nh, a, sa, s);
+			}
+			HIP_TRY(hipGetLastError());
+		}
+	}
+	if(timing){ HIP_TRY(hipEventRecord(ev.ev[1], s)); }
+	HIP_TRY(hipStreamSynchronize(s));
+	if(timing){ HIP_TRY(hipEventElapsedTime(ms, ev.ev[0], ev.ev[1])); }
+	return KWAGE_OK;
+}
+
+namespace {
+
 // The whole search, queued on the context's first stream and waited for.
 int search_scores_device(kwage_group *g, kwage_batch *b, void *scores_dev, uint64_t row_elems, void *num_query_kmer_dev,
                          uint32_t flags, float *search_kernel_ms, PoolBlocks &blocks, const char *what)
@@ -120,33 +231,9 @@ int search_scores_device(kwage_group *g, kwage_batch *b, void *scores_dev, uint6
 		return fail(KWAGE_ERR_ARG, "a query of %llu k-mer positions x %u hash functions exceeds 2^32 rows", (unsigned long long)L->max_pos, nh);
 	}
 	const uint32_t n = b->n;
-	const uint64_t span = g->next_byte*8;
-	SearchArgs a;
-	memset(&a, 0, sizeof(a));
-	a.units_per_row = (uint32_t)(g->stride/16);
-	a.chunks = (a.units_per_row + WAVE - 1)/WAVE;
-	if((uint64_t)n*a.chunks > 0xFFFFFFFFull){ return fail(KWAGE_ERR_ARG, "batch too large for one launch"); }
-	// the launches' shapes, planned (and refused) before the first kernel
-	uint32_t planes = 0, seg_planes = 0, slice = n;
-	if(n && span){
-		planes = planes_for(L->max_pos);
-		a.n_queries = n;
-		choose_segments(a, L->max_pos, 1024, ctx->tune.force_segs);
-		seg_planes = (a.segs > 1) ? planes_for(a.seg_kmers) : planes;
-		if(a.segs > 1){      // keep the slab of partial counters bounded: fewer queries per slice
-			const uint64_t slab_per_q = (uint64_t)a.segs*seg_planes*g->stride;
-			slice = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(slice, SLAB_BYTES_PER_SLICE/slab_per_q));
-			// score_combine_kernel's grid is one workgroup per (query, tile): a slice's threads stay below 2^32
-			const uint64_t max_wgs = 0xFFFFFFFFull/(COMBINE_WAVES*WAVE);
-			if(a.chunks > max_wgs){ return fail(KWAGE_ERR_ARG, "batch too large for one launch"); }
-			slice = (uint32_t)std::min<uint64_t>(slice, max_wgs/a.chunks);
-		}
-		if((uint64_t)slice*a.segs*a.chunks/4 + 1 > 0x7FFFFFFFull){ return fail(KWAGE_ERR_ARG, "batch too large for one launch"); }
-	}
+	ScorePlan plan;
+	if((rc = score_stage_plan(g, n, L->max_pos, &plan))){ return rc; }
 	hipStream_t s = ctx->stream;
-	const bool timing = (flags & KWAGE_SEARCH_TIMING) != 0 && search_kernel_ms;
-	Events ev;
-	if(timing){ for(hipEvent_t &e : ev.ev){ HIP_TRY(hipEventCreate(&e)); } }
 
 	uint32_t *d_rows = nullptr, *d_nkmer = nullptr, *d_qthr = nullptr;
 	unsigned long long *d_tables = nullptr, *d_missing = nullptr;
@@ -174,60 +261,19 @@ int search_scores_device(kwage_group *g, kwage_batch *b, void *scores_dev, uint6
 				return fail(KWAGE_ERR_STATE, "%llu row indices of this batch are not among the rows of the sparse group (it was created for other queries)", missing);
 			}
 		}
+		// (the k-mer counts are final here: their copy is queued ahead of the score stage, which waits for the stream)
+		if(num_query_kmer_dev){
+			HIP_TRY(hipMemcpyAsync(num_query_kmer_dev, d_nkmer, (size_t)n*sizeof(uint32_t), hipMemcpyDefault, s));
+		}
 	}
 
-	// ---- scores: tile kernels, or segments + combine slice by slice of the queries ---------------------------------------
-	if(timing){ HIP_TRY(hipEventRecord(ev.ev[0], s)); }
-	if(n && span){
-		a.db = g->d_bits;
-		a.stride = g->stride;
-		a.valid = g->d_valid;
-		a.rows = d_rows;
-		a.num_hash = nh;
-		ScoreArgs sa;
-		sa.row_elems = row_elems;
-		sa.span = span;
-		sa.form = (ctx->tune.scores_form == (int64_t)SCORES_FORM_LANE) ? SCORES_FORM_LANE : SCORES_FORM_WAVE;
-		if(a.segs > 1){
-			uint32_t *slab = nullptr;
-			if((rc = blocks.take((uint64_t)slice*a.segs*seg_planes*g->stride, &slab))){ return rc; }
-			a.partial = slab;
-			snprintf(last_kernel, sizeof(last_kernel), "count_kernel<%u,%u>+score_combine_kernel<%u>", seg_planes, std::min(nh, 5u), planes);
-		}
-		else{
-			snprintf(last_kernel, sizeof(last_kernel), "score_tile_kernel<%u,%u>", planes, std::min(nh, 5u));
-		}
-		for(uint32_t q0 = 0; q0 < n; q0 += slice){
-			a.n_queries = std::min(slice, n - q0);
-			a.pos_off = L->d_pos_off + q0;
-			a.nkmer = d_nkmer + q0;
-			a.qthr = d_qthr + q0;
-			sa.out = (uint32_t*)scores_dev + (uint64_t)q0*row_elems;
-			if(a.segs > 1){
-				by_shape<SegLaunch>(seg_planes, nh, a, s);
-				HIP_TRY(hipGetLastError());
-				switch(planes){
-					case 7: rc = launch_combine<7>(a, sa, seg_planes, s); break;
-					case 10: rc = launch_combine<10>(a, sa, seg_planes, s); break;
-					case 14: rc = launch_combine<14>(a, sa, seg_planes, s); break;
-					case 20: rc = launch_combine<20>(a, sa, seg_planes, s); break;
-					default: rc = launch_combine<32>(a, sa, seg_planes, s); break;
-				}
-				if(rc){ return rc; }
-			}
-			else{
-				by_shape<TileLaunch>(planes, nh, a, sa, s);
-			}
-			HIP_TRY(hipGetLastError());
-		}
-	}
-	if(timing){ HIP_TRY(hipEventRecord(ev.ev[1], s)); }
-	if(num_query_kmer_dev && n){
-		HIP_TRY(hipMemcpyAsync(num_query_kmer_dev, d_nkmer, (size_t)n*sizeof(uint32_t), hipMemcpyDefault, s));
-	}
-	HIP_TRY(hipStreamSynchronize(s));
-	if(timing){ HIP_TRY(hipEventElapsedTime(search_kernel_ms, ev.ev[0], ev.ev[1])); }
-	return KWAGE_OK;
+	const RowListView v = {d_rows, L->d_pos_off, d_nkmer, n, L->max_pos, nh};
+	ScoreArgs sa;
+	sa.out = (uint32_t*)scores_dev;
+	sa.row_elems = row_elems;
+	sa.span = 0;
+	sa.form = SCORES_FORM_WAVE;
+	return score_stage_run(g, v, plan, sa, flags, search_kernel_ms, blocks, last_kernel);
 }
 
 // The host form: the matrix in a block of the context's pool (rows `span` cells apart), then one strided copy that

@@ -18,16 +18,9 @@
 #ifndef KWAGE_AMD_SCORES_KERNELS_HPP
 #define KWAGE_AMD_SCORES_KERNELS_HPP
 
+#include "score_stage.hpp"      // ScoreArgs, SCORES_FORM_*
+
 namespace kwage {
-
-static constexpr uint32_t SCORES_FORM_WAVE = 0, SCORES_FORM_LANE = 1;
-
-struct ScoreArgs {
-	uint32_t *out;                  // cell (q, c) of the launch's queries at out[q*row_elems + c]
-	unsigned long long row_elems;   // cells between rows (multiple of 4, >= span)
-	unsigned long long span;        // columns of the group (multiple of 8): cells at or beyond it are never written
-	uint32_t form;                  // SCORES_FORM_*
-};
 
 // lanes whose planes lie in LDS at a time in the wave form: PLANES x lanes x 16 B <= 4 KiB per wave
 template <int PLANES> struct ScoreXch { static constexpr int LANES = (PLANES <= 14) ? 16 : 8; };

@@ -112,6 +112,8 @@ class Group:
         self.params = Params(kmer_len, num_hash, log_2_filter_len, hash_func)
         self._h = C.c_void_p()
         self._nrows = 1 << log_2_filter_len          # rows an add_columns() image must hold
+        self._real: List[Tuple[int, int]] = []       # (first column, columns) of everything added: the rest of the span is padding
+        self._column_bits = None                     # column_bits(), once computed
         check(lib().kwage_group_create(ctx._h, C.byref(self.params), column_capacity, C.byref(self._h)))
 
     @classmethod
@@ -125,6 +127,8 @@ class Group:
         g.params = Params(kmer_len, num_hash, log_2_filter_len, hash_func)
         g._h = C.c_void_p()
         g._nrows = int(rows.size)                     # a sparse group's images hold the listed rows only
+        g._real = []
+        g._column_bits = None
         check(lib().kwage_group_create_sparse(ctx._h, C.byref(g.params), column_capacity, rows.ctypes.data, rows.size, C.byref(g._h)))
         return g
 
@@ -140,11 +144,13 @@ class Group:
         assert rows.shape[0] == self._nrows and rows.shape[1] >= (num_filter + 7) // 8, (rows.shape, self._nrows, num_filter)
         first = C.c_uint64()
         check(lib().kwage_group_add_columns(self._h, rows.ctypes.data, rows.strides[0], num_filter, C.byref(first)))
+        self._real.append((first.value, num_filter))
         return first.value
 
     def add_db_file(self, path: str) -> Tuple[int, int]:
         first, nf = C.c_uint64(), C.c_uint32()
         check(lib().kwage_group_add_db_file(self._h, path.encode(), C.byref(first), C.byref(nf)))
+        self._real.append((first.value, nf.value))
         return first.value, nf.value
 
     def add_db_files(self, paths: Sequence[str]) -> List[Tuple[int, int]]:
@@ -153,11 +159,13 @@ class Group:
         arr = (C.c_char_p * n)(*[p.encode() for p in paths])
         first, nf = (C.c_uint64 * n)(), (C.c_uint32 * n)()
         check(lib().kwage_group_add_db_files(self._h, arr, n, first, nf))
+        self._real.extend((int(first[i]), int(nf[i])) for i in range(n))
         return [(int(first[i]), int(nf[i])) for i in range(n)]
 
     def add_random_columns(self, num_columns: int, seed: int, density_q8: int) -> int:
         first = C.c_uint64()
         check(lib().kwage_group_add_random_columns(self._h, num_columns, seed, density_q8, C.byref(first)))
+        self._real.append((first.value, num_columns))
         return first.value
 
     def set_bits(self, rows: np.ndarray, columns: np.ndarray) -> None:
@@ -174,6 +182,22 @@ class Group:
 
     def finalize(self) -> None:
         check(lib().kwage_group_finalize(self._h))
+
+    def real_columns(self) -> np.ndarray:
+        """bool [column_span]: the columns that hold a sample (the rest pads files to their byte boundaries)."""
+        real = np.zeros(self.column_span, dtype=bool)
+        for first, nf in self._real:
+            real[first:first + nf] = True
+        return real
+
+    def column_bits(self) -> np.ndarray:
+        """kwage_group_column_bits(): the set-bit count of every column (uint32 [column_span], 0 on pad columns) -- the
+        denominator of a Jaccard index.  Computed once per group and kept (a group is finalized: it no longer changes)."""
+        if self._column_bits is None:
+            out = np.zeros(self.column_span, dtype=np.uint32)
+            check(lib().kwage_group_column_bits(self._h, out.ctypes.data if out.size else None))
+            self._column_bits = out
+        return self._column_bits
 
     num_columns = property(lambda self: lib().kwage_group_num_columns(self._h))
     column_span = property(lambda self: lib().kwage_group_column_span(self._h))
@@ -386,6 +410,83 @@ def search_scores_device(group: Group, batch: Batch, out, num_query_kmer=None, f
     return ScoreResult(out, num_query_kmer, (lib().kwage_search_scores_kernel() or b"").decode(), float(ms.value))
 
 
+class FilterSet:
+    """Whole Bloom filters as the questions of a search (kwage_filterset): their set rows as ascending row lists on the
+    device.  Belongs to its context; close() it before the context."""
+
+    def __init__(self, ctx: Context, params: Params, handle):
+        self.ctx, self.params, self._h = ctx, params, handle
+
+    @classmethod
+    def from_columns(cls, group: Group, cols: Sequence[int]) -> "FilterSet":
+        """The filters of the given global columns of a finalized, non-sparse group (kwage_filterset_from_columns)."""
+        cols = np.ascontiguousarray(cols, dtype=np.uint64)
+        h = C.c_void_p()
+        check(lib().kwage_filterset_from_columns(group._h, cols.ctypes.data if cols.size else None, cols.size, C.byref(h)))
+        p = group.params
+        return cls(group.ctx, Params(p.kmer_len, p.num_hash, p.log_2_filter_len, p.hash_func), h)
+
+    @classmethod
+    def from_bits(cls, ctx: Context, kmer_len: int, num_hash: int, log_2_filter_len: int, bits: np.ndarray, hash_func: int = 0) -> "FilterSet":
+        """bits: uint8 [n, max(1, 2^L / 8)] host bit vectors, LSB first -- `.bloom` payloads, kwage_bloom_bits_from_batch's
+        output (kwage_filterset_from_bits)."""
+        bits = np.asarray(bits)
+        if bits.dtype != np.uint8 or bits.ndim != 2 or bits.shape[1] != max(1, (1 << log_2_filter_len) // 8):
+            raise ValueError("bits: uint8 [n, %d] required, got %s %s" % (max(1, (1 << log_2_filter_len) // 8), bits.dtype, bits.shape))
+        bits = np.ascontiguousarray(bits)
+        p = Params(kmer_len, num_hash, log_2_filter_len, hash_func)
+        h = C.c_void_p()
+        check(lib().kwage_filterset_from_bits(ctx._h, C.byref(p), bits.ctypes.data if bits.size else None, bits.shape[1], bits.shape[0], C.byref(h)))
+        return cls(ctx, p, h)
+
+    def close(self) -> None:
+        if self._h:
+            lib().kwage_filterset_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __len__(self) -> int:
+        return int(lib().kwage_filterset_num_filters(self._h))
+
+    n = property(__len__)
+
+    def bit_counts(self) -> np.ndarray:
+        out = np.zeros(len(self), dtype=np.uint32)
+        check(lib().kwage_filterset_bit_counts(self._h, out.ctypes.data if out.size else None))
+        return out
+
+    def rows(self, i: int) -> np.ndarray:
+        """Diagnostic: the row list of filter i, copied back (kwage_filterset_read_rows)."""
+        count = C.c_uint64()
+        check(lib().kwage_filterset_read_rows(self._h, i, None, 0, C.byref(count)))
+        out = np.zeros(count.value, dtype=np.uint32)
+        check(lib().kwage_filterset_read_rows(self._h, i, out.ctypes.data if out.size else None, out.size, C.byref(count)))
+        return out
+
+
+def search_filter_scores(group: Group, fs: FilterSet, flags: int = 0) -> ScoreResult:
+    """kwage_search_filter_scores(): uint32 [filters, column_span], cell (i, c) = rows set in both filter i and column c
+    (pad columns: 0).  num_query_kmer holds the filters' set-bit counts."""
+    n, span = len(fs), group.column_span
+    scores = np.zeros((n, span), dtype=np.uint32)
+    ms = C.c_float(0)
+    check(lib().kwage_search_filter_scores(group._h, fs._h, scores.ctypes.data if scores.size else None, span, flags, C.byref(ms)))
+    return ScoreResult(scores, fs.bit_counts(), (lib().kwage_search_filter_kernel() or b"").decode(), float(ms.value))
+
+
+def search_filter_scores_device(group: Group, fs: FilterSet, out, flags: int = 0) -> ScoreResult:
+    """kwage_search_filter_scores_device(): the same matrix written into `out`, an int32 device tensor
+    [filters, >= column_span] laid out as search_scores_device wants it; columns at or beyond the span are left alone."""
+    import torch
+    _device_tensor(out, "out", torch.int32, row_multiple=4)
+    n, span = len(fs), group.column_span
+    if out.dim() != 2 or out.shape[0] != n or out.shape[1] < span:
+        raise ValueError("out: shape [%d, >= %d] required, got %s" % (n, span, tuple(out.shape)))
+    row_elems = out.stride(0) if out.shape[0] > 1 else span
+    ms = C.c_float(0)
+    check(lib().kwage_search_filter_scores_device(group._h, fs._h, out.data_ptr() or None, row_elems, flags, C.byref(ms)))
+    return ScoreResult(out, None, (lib().kwage_search_filter_kernel() or b"").decode(), float(ms.value))
+
+
 class PendingSearch:
     """A submitted search (kwage_search_submit); collect() waits for it and returns the result."""
 
@@ -413,6 +514,7 @@ Group.search = lambda self, batch, threshold, flags=0: search(self, batch, thres
 Group.search_topk = lambda self, batch, k, threshold=0.0, flags=0: search_topk(self, batch, k, threshold, flags)
 Group.submit = lambda self, batch, threshold, flags=0: submit(self, batch, threshold, flags)
 Group.search_scores = lambda self, batch, flags=0: search_scores(self, batch, flags)
+Group.search_filter_scores = lambda self, fs, flags=0: search_filter_scores(self, fs, flags)
 
 
 def hash_batch(ctx: Context, kmer_len: int, num_hash: int, log_2_filter_len: int, batch: Batch
@@ -502,6 +604,48 @@ class Database:
         for g, base in zip(self.groups, bases):
             if batch.n and g.column_span:
                 search_scores_device(g, batch, out[:, base:base + g.column_span])
+        return out
+
+    def similar(self, fs: "FilterSet", k: int) -> List[List[Tuple[int, int, int, int, int, float]]]:
+        """Per filter of the set, the k samples of the database most like it by Jaccard index: the filter search of every
+        group side by side in one int32 device tensor (as search_scores lays it out), then, in float64,
+        shared / (filter_bits + column_bits - shared) -- 0 where that union is empty -- and each filter's first k real
+        columns under (Jaccard descending, global column ascending) by a stable sort.  Groups whose parameters differ
+        from the set's are left out: their filters are not comparable.  Returns per filter
+        [(group index, column, shared, filter_bits, column_bits, jaccard), ...] in that order."""
+        import torch
+        n = len(fs)
+        out: List[List[Tuple[int, int, int, int, int, float]]] = [[] for _ in range(n)]
+        key = lambda p: (p.kmer_len, p.num_hash, p.log_2_filter_len, p.hash_func)
+        groups = [(gi, g) for gi, g in enumerate(self.groups) if key(g.params) == key(fs.params) and g.column_span]
+        if not n or not groups or k <= 0:
+            return out
+        dev = torch.device("cuda", groups[0][1].ctx.device)
+        bases, at = [], 0
+        for _, g in groups:
+            bases.append(at)
+            at += g.column_span
+        shared = torch.empty((n, at), dtype=torch.int32, device=dev)
+        for (_, g), base in zip(groups, bases):
+            search_filter_scores_device(g, fs, shared[:, base:base + g.column_span])
+        col_bits = torch.from_numpy(np.concatenate([g.column_bits() for _, g in groups]).astype(np.int64)).to(dev)
+        real = torch.from_numpy(np.concatenate([g.real_columns() for _, g in groups])).to(dev)
+        f_bits = torch.from_numpy(fs.bit_counts().astype(np.int64)).to(dev)
+        sh = shared.to(torch.int64)
+        union = f_bits[:, None] + col_bits[None, :] - sh
+        jac = torch.where(union > 0, sh.to(torch.float64) / union.clamp(min=1).to(torch.float64), torch.zeros((), dtype=torch.float64, device=dev))
+        jac = torch.where(real[None, :], jac, torch.full((), -1.0, dtype=torch.float64, device=dev))      # pad columns: behind every sample
+        # (torch.topk leaves the order of ties open; a stable sort keeps equal values in column order)
+        order = torch.sort(jac, dim=1, descending=True, stable=True).indices[:, :min(int(k), at)]
+        take = lambda t: torch.gather(t, 1, order).cpu().numpy()
+        o, j, s_, r = order.cpu().numpy(), take(jac), take(sh), take(real[None, :].expand(n, at))
+        cb, fb = col_bits.cpu().numpy(), f_bits.cpu().numpy()
+        import bisect
+        for i in range(n):
+            for c, jv, sv, ok in zip(o[i].tolist(), j[i].tolist(), s_[i].tolist(), r[i].tolist()):
+                if ok:
+                    gpos = bisect.bisect_right(bases, c) - 1
+                    out[i].append((groups[gpos][0], c - bases[gpos], int(sv), int(fb[i]), int(cb[c]), float(jv)))
         return out
 
     def close(self) -> None:
@@ -629,6 +773,41 @@ class FileDatabase(Database):
         finally:
             b.close()
         return np.ascontiguousarray(full[:, cols]), accessions
+
+    def similar_samples(self, accessions: Sequence[str], k: int) -> List[Tuple[str, List[Tuple[str, str, int, int, int, int, float]]]]:
+        """Per run accession, the k samples of the database most like it (Database.similar on its column): each accession
+        is the first (file, column) carrying it, in file order; one not found raises KeyError.  Returns
+        [(accession, [(sample accession, path, column in the file, shared, query_bits, sample_bits, jaccard), ...]), ...]."""
+        import bisect
+        where = {}
+        for gi, layout in enumerate(self._layout):
+            for first, nf, path in layout:
+                where[path] = (gi, first, nf)
+        found = {}
+        for f in self.files:
+            gi, first, nf = where[f]
+            for c in range(nf):
+                found.setdefault(self._accession(f, c), (gi, first + c))
+        for a in accessions:
+            if a not in found:
+                raise KeyError("no sample with run accession %s in the database" % a)
+        result = [None] * len(accessions)
+        for gi in sorted({found[a][0] for a in accessions}):
+            mine = [i for i, a in enumerate(accessions) if found[a][0] == gi]
+            fs = FilterSet.from_columns(self.groups[gi], [found[accessions[i]][1] for i in mine])
+            try:
+                lists = self.similar(fs, k)
+            finally:
+                fs.close()
+            for i, lst in zip(mine, lists):
+                rec = []
+                for g2, c, sh, fb, cb, jv in lst:
+                    layout = self._layout[g2]
+                    at = bisect.bisect_right([f[0] for f in layout], c) - 1
+                    first, _, path = layout[at]
+                    rec.append((self._accession(path, c - first), path, c - first, sh, fb, cb, jv))
+                result[i] = (accessions[i], rec)
+        return result
 
     def close(self) -> None:
         for d in self._info.values():

@@ -13,6 +13,7 @@ KWAGE_DBTOOL_BIN = os.path.join(_HERE, "bin", "kwage_dbtool")
 KWAGE_TOP_BIN = os.path.join(_HERE, "bin", "kwage_top")
 KWAGE_TOP_NODE_BIN = os.path.join(_HERE, "bin", "kwage_top_node")
 KWAGE_SCORES_BIN = os.path.join(_HERE, "bin", "kwage_scores")
+KWAGE_NEAR_BIN = os.path.join(_HERE, "bin", "kwage_near")
 TOPK_MAX = 1024              # KWAGE_TOPK_MAX
 
 
@@ -46,7 +47,7 @@ def build_native(force: bool = False) -> str:
 def ensure_built() -> str:
     """Build the native library + CLI if (and only if) they are missing.  Used by bench.py / smoke();
     compiling the HIP extension is not a fallback -- nothing runs without it."""
-    if not all(os.path.exists(p) for p in (_LIB, KWAGE_BIN, KWAGE_TOP_BIN, KWAGE_SCORES_BIN, KWAGE_DBTOOL_BIN)):
+    if not all(os.path.exists(p) for p in (_LIB, KWAGE_BIN, KWAGE_TOP_BIN, KWAGE_SCORES_BIN, KWAGE_NEAR_BIN, KWAGE_DBTOOL_BIN)):
         build_native()
     return _LIB
 
@@ -141,6 +142,17 @@ _SIGNATURES = [
     ("kwage_search_scores_device", C.c_int, [_P, _P, _P, C.c_uint64, _P, C.c_uint32, C.POINTER(C.c_float)]),
     ("kwage_search_scores", C.c_int, [_P, _P, _P, C.c_uint64, _P, C.c_uint32, C.POINTER(C.c_float)]),
     ("kwage_search_scores_kernel", C.c_char_p, []),
+    ("kwage_filterset_from_columns", C.c_int, [_P, _P, C.c_uint32, C.POINTER(_P)]),
+    ("kwage_filterset_from_bits", C.c_int, [_P, C.POINTER(Params), _P, C.c_uint64, C.c_uint32, C.POINTER(_P)]),
+    ("kwage_filterset_destroy", None, [_P]),
+    ("kwage_filterset_num_filters", C.c_uint32, [_P]),
+    ("kwage_filterset_bit_counts", C.c_int, [_P, _P]),
+    ("kwage_filterset_read_rows", C.c_int, [_P, C.c_uint32, _P, C.c_uint64, C.POINTER(C.c_uint64)]),
+    ("kwage_search_filter_scores_device", C.c_int, [_P, _P, _P, C.c_uint64, C.c_uint32, C.POINTER(C.c_float)]),
+    ("kwage_search_filter_scores", C.c_int, [_P, _P, _P, C.c_uint64, C.c_uint32, C.POINTER(C.c_float)]),
+    ("kwage_search_filter_kernel", C.c_char_p, []),
+    ("kwage_group_column_bits", C.c_int, [_P, _P]),
+    ("kwage_group_column_bits_device", C.c_int, [_P, _P]),
     ("kwage_search_submit", C.c_int, [_P, _P, C.c_float, C.c_uint32, C.POINTER(_P)]),
     ("kwage_search_collect", C.c_int, [_P, C.POINTER(C.POINTER(Result))]),
     ("kwage_search_poll", C.c_int, [_P]),
