@@ -377,6 +377,39 @@ void choose_segments(SearchArgs &a, uint64_t max_kmers, uint64_t max_segs, int64
 	a.segs = (uint32_t)((max_kmers + a.seg_kmers - 1)/a.seg_kmers);
 }
 
+int fail_missing_rows(unsigned long long missing)
+{
+	return fail(KWAGE_ERR_STATE, "%llu row indices of this batch are not among the rows of the sparse group (it was created for other queries)", missing);
+}
+
+uint32_t tile_chunks(const kwage_group *g) { return ((uint32_t)(g->stride/16) + WAVE - 1)/WAVE; }
+
+int plan_tiles(const kwage_group *g, uint64_t max_count, uint32_t slice, uint64_t max_combine_wgs, TilePlan *plan)
+{
+	static const uint64_t SLAB_BYTES_PER_SLICE = 1ull << 30;       // partial counters of one slice of the queries (segmented form)
+	SearchArgs a;
+	memset(&a, 0, sizeof(a));
+	a.chunks = tile_chunks(g);
+	uint32_t planes = 0, seg_planes = 0;
+	if(slice){
+		planes = planes_for(max_count);
+		a.n_queries = slice;
+		choose_segments(a, max_count, 1024, g->ctx->tune.force_segs);
+		seg_planes = (a.segs > 1) ? planes_for(a.seg_kmers) : planes;
+		if(a.segs > 1){      // keep the slab of partial counters bounded: fewer queries per slice
+			const uint64_t slab_per_q = (uint64_t)a.segs*seg_planes*g->stride;
+			slice = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(slice, SLAB_BYTES_PER_SLICE/slab_per_q));
+			if(max_combine_wgs){
+				if(a.chunks > max_combine_wgs){ return fail(KWAGE_ERR_ARG, "batch too large for one launch"); }
+				slice = (uint32_t)std::min<uint64_t>(slice, max_combine_wgs/a.chunks);
+			}
+		}
+		if((uint64_t)slice*a.segs*a.chunks/4 + 1 > 0x7FFFFFFFull){ return fail(KWAGE_ERR_ARG, "batch too large for one launch"); }
+	}
+	*plan = TilePlan{(uint32_t)(g->stride/16), a.chunks, planes, seg_planes, a.segs, a.seg_kmers, slice};
+	return KWAGE_OK;
+}
+
 }  // namespace kwage
 
 namespace {
@@ -1285,8 +1318,7 @@ int collect_search_steps(Slot *sl, SearchOutcome *out)
 		HIP_TRY(hipStreamSynchronize(sl->stream));     // (polling an event instead measured no faster)
 		const uint64_t *hc = (const uint64_t*)sl->h_stage.p;
 		if(hc[2] != 0){
-			return fail(KWAGE_ERR_STATE, "%llu row indices of this batch are not among the rows of the sparse group (it was created for other queries)",
-			            (unsigned long long)hc[2]);
+			return fail_missing_rows(hc[2]);
 		}
 		out->n_hits = hc[0];
 		out->total_kmers = 0;

@@ -4,8 +4,8 @@
 //
 //   engine.hip   contexts, tuning knobs, query batches, the search pipeline (k-mer stage, gather kernels, hit lists)
 //   loader.hip   database groups: allocation, the loaders (.db files raw and compressed, sparse groups), synthetic columns
-//   topk.hip     the top-k search: engine.hip's batch layout, k-mer stage, counter widths, segment rule and result block
-//                (declared at the end of this file), then its own selection kernels
+//   topk.hip     the top-k search: engine.hip's batch layout, k-mer stage, counter widths, segment rule, tile plan and
+//                result block (declared at the end of this file), then its own selection kernels (tile_search.hpp runs them)
 //   scores.hip   the dense score search: the same shared stages, then its own expand-and-store kernels (score_stage.hpp)
 //   filterset.hip  filter sets (row lists made from whole Bloom filters) and the filter search, which runs scores.hip's stage
 #ifndef KWAGE_AMD_ENGINE_STATE_HPP
@@ -479,6 +479,35 @@ uint32_t planes_for(uint64_t max_count);
 // Sets a.segs / a.seg_kmers from a.n_queries and a.chunks: how many segments each query's k-mer list is cut into, at
 // most max_segs (force_segs > 0: the tuning knob's count instead of the rule's).
 void choose_segments(SearchArgs &a, uint64_t max_kmers, uint64_t max_segs, int64_t force_segs);
+
+// The refusal of a batch whose row indices a sparse group does not hold (KWAGE_ERR_STATE), for every search kind.
+int fail_missing_rows(unsigned long long missing);
+
+// n row lists on the device, the shape SearchArgs::rows / pos_off / nkmer have: list i is the counts[i] entries
+// [num_hash row indices each] from rows[pos_off[i]*num_hash] on.  max_count: the longest list (it picks the counters'
+// width).  Every row index addresses a row of the group the view is searched in.
+struct RowListView {
+	const uint32_t *rows;
+	const uint64_t *pos_off;        // n + 1
+	const uint32_t *counts;         // n
+	uint32_t n;
+	uint64_t max_count;
+	uint32_t num_hash;
+};
+
+// The launches of a counted tile search (top-k, scores, filter scores; tile_search.hpp runs them), planned on the host.
+struct TilePlan {
+	uint32_t units_per_row, chunks; // 16-byte units and KiB tiles of a row of the group
+	uint32_t planes, seg_planes;    // counter widths of the whole list and of one segment
+	uint32_t segs, seg_kmers;
+	uint32_t slice;                 // lists per launch
+};
+uint32_t tile_chunks(const kwage_group *g);
+// Plans the search of lists of at most max_count entries, `slice` at a time at most (0: nothing to launch -- only
+// units_per_row and chunks are set): the segments, chosen for a launch of `slice` lists, and a slice the slab of the
+// segments' partial counters bounds, and max_combine_wgs (query, tile) pairs where it is not 0.  KWAGE_ERR_ARG where a
+// slice is too large for one launch.
+int plan_tiles(const kwage_group *g, uint64_t max_count, uint32_t slice, uint64_t max_combine_wgs, TilePlan *plan);
 
 // What a kwage_result* points into, for every search kind: kwage_result_free() deletes it.
 struct ResultStorage {

@@ -226,7 +226,7 @@ int filter_scores_device(kwage_group *g, kwage_filterset *fs, void *scores_dev, 
 		return fail(KWAGE_ERR_ARG, "%s: the score matrix must be a 16-byte aligned device pointer", what);
 	}
 	if((rc = set_device(g->ctx))){ return rc; }
-	ScorePlan plan;
+	TilePlan plan;
 	if((rc = score_stage_plan(g, fs->n, fs->max_count, &plan))){ return rc; }
 	// one row per entry, whatever the group's hash count: the list IS the filter's set rows
 	const RowListView v = {(const uint32_t*)fs->rows.p, (const uint64_t*)fs->prefix.p, (const uint32_t*)fs->counts.p, fs->n, fs->max_count, 1};
@@ -242,19 +242,12 @@ int filter_scores_host(kwage_group *g, kwage_filterset *fs, uint32_t *scores, ui
 {
 	int rc;
 	static const char *what = "kwage_search_filter_scores";
-	const uint64_t span = g->next_byte*8;
-	const uint32_t n = fs->n;
 	if((rc = filter_scores_check(g, fs, row_elems, what))){ return rc; }
-	if(n && span && !scores){ return fail(KWAGE_ERR_ARG, "%s: scores is NULL", what); }
-	if((rc = set_device(g->ctx))){ return rc; }
-	uint32_t *d_scores = nullptr;
-	if((rc = blocks.take(std::max<uint64_t>((uint64_t)n*span, 4)*sizeof(uint32_t), &d_scores))){ return rc; }
-	if((rc = filter_scores_device(g, fs, d_scores, span, flags, ms, blocks, what))){ return rc; }
-	if(n && span){
-		hipStream_t s = g->ctx->stream;
-		HIP_TRY(hipMemcpy2DAsync(scores, row_elems*sizeof(uint32_t), d_scores, span*sizeof(uint32_t), span*sizeof(uint32_t), n, hipMemcpyDeviceToHost, s));
-		HIP_TRY(hipStreamSynchronize(s));
-	}
+	rc = scores_to_host(g, fs->n, scores, row_elems, blocks, what, [&](uint32_t *d_scores, uint64_t span) {
+		return filter_scores_device(g, fs, d_scores, span, flags, ms, blocks, what);
+	});
+	if(rc){ return rc; }
+	if(fs->n && g->next_byte){ HIP_TRY(hipStreamSynchronize(g->ctx->stream)); }
 	return KWAGE_OK;
 }
 
@@ -271,7 +264,7 @@ int column_bits_device(kwage_group *g, void *out_dev, PoolBlocks &blocks, const 
 	kwage_ctx *ctx = g->ctx;
 	if((rc = set_device(ctx))){ return rc; }
 	const uint64_t nrows = g->nrows;
-	ScorePlan plan;
+	TilePlan plan;
 	if((rc = score_stage_plan(g, 1, nrows, &plan))){ return rc; }
 	void *p = nullptr;
 	uint64_t cap = 0;
@@ -301,16 +294,6 @@ int column_bits_device(kwage_group *g, void *out_dev, PoolBlocks &blocks, const 
 	return score_stage_run(g, v, plan, sa, 0, nullptr, blocks, name);
 }
 
-// An error return may leave kernels of the call queued: nothing of it may still run when its device blocks go back to
-// the pool (the destructors that follow).
-void settle(kwage_ctx *ctx, int rc)
-{
-	if(rc && ctx){
-		(void)hipStreamSynchronize(ctx->stream);
-		(void)hipGetLastError();
-	}
-}
-
 }  // namespace
 }  // namespace kwage
 
@@ -321,8 +304,7 @@ extern "C" int kwage_filterset_from_columns(kwage_group *g, const uint64_t *colu
 	int rc;
 	{
 		kwage::PoolBlocks blocks(&g->ctx->batch_pool);
-		rc = kwage::from_columns(g, columns, n, fs.get(), blocks);
-		kwage::settle(g->ctx, rc);
+		rc = kwage::settle(g->ctx, kwage::from_columns(g, columns, n, fs.get(), blocks));
 	}
 	if(rc){ return rc; }
 	*out = fs.release();
@@ -337,8 +319,7 @@ extern "C" int kwage_filterset_from_bits(kwage_ctx *ctx, const kwage_params *par
 	int rc;
 	{
 		kwage::PoolBlocks blocks(&ctx->batch_pool);
-		rc = kwage::from_bits(ctx, params, bits, filter_stride_bytes, n, fs.get(), blocks);
-		kwage::settle(ctx, rc);
+		rc = kwage::settle(ctx, kwage::from_bits(ctx, params, bits, filter_stride_bytes, n, fs.get(), blocks));
 	}
 	if(rc){ return rc; }
 	*out = fs.release();
@@ -382,9 +363,7 @@ extern "C" int kwage_search_filter_scores_device(kwage_group *g, kwage_filterset
 {
 	if(!g || !fs){ return kwage::fail(KWAGE_ERR_ARG, "kwage_search_filter_scores_device: NULL argument"); }
 	kwage::PoolBlocks blocks(&g->ctx->batch_pool);
-	const int rc = kwage::filter_scores_device(g, fs, scores_dev, row_elems, flags, search_kernel_ms, blocks, "kwage_search_filter_scores_device");
-	kwage::settle(g->ctx, rc);
-	return rc;
+	return kwage::settle(g->ctx, kwage::filter_scores_device(g, fs, scores_dev, row_elems, flags, search_kernel_ms, blocks, "kwage_search_filter_scores_device"));
 }
 
 extern "C" int kwage_search_filter_scores(kwage_group *g, kwage_filterset *fs, uint32_t *scores, uint64_t row_elems, uint32_t flags,
@@ -392,9 +371,7 @@ extern "C" int kwage_search_filter_scores(kwage_group *g, kwage_filterset *fs, u
 {
 	if(!g || !fs){ return kwage::fail(KWAGE_ERR_ARG, "kwage_search_filter_scores: NULL argument"); }
 	kwage::PoolBlocks blocks(&g->ctx->batch_pool);
-	const int rc = kwage::filter_scores_host(g, fs, scores, row_elems, flags, search_kernel_ms, blocks);
-	kwage::settle(g->ctx, rc);
-	return rc;
+	return kwage::settle(g->ctx, kwage::filter_scores_host(g, fs, scores, row_elems, flags, search_kernel_ms, blocks));
 }
 
 extern "C" const char *kwage_search_filter_kernel(void) { return kwage::last_kernel; }
@@ -403,9 +380,7 @@ extern "C" int kwage_group_column_bits_device(kwage_group *g, void *out_dev)
 {
 	if(!g){ return kwage::fail(KWAGE_ERR_ARG, "kwage_group_column_bits_device: NULL argument"); }
 	kwage::PoolBlocks blocks(&g->ctx->batch_pool);
-	const int rc = kwage::column_bits_device(g, out_dev, blocks, "kwage_group_column_bits_device");
-	kwage::settle(g->ctx, rc);
-	return rc;
+	return kwage::settle(g->ctx, kwage::column_bits_device(g, out_dev, blocks, "kwage_group_column_bits_device"));
 }
 
 extern "C" int kwage_group_column_bits(kwage_group *g, uint32_t *out)
@@ -422,6 +397,5 @@ extern "C" int kwage_group_column_bits(kwage_group *g, uint32_t *out)
 	if(!rc && span && hipMemcpy(out, d_out, (size_t)span*sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess){
 		rc = kwage::fail(KWAGE_ERR_DEVICE, "%s: copying the counts back failed", what);
 	}
-	kwage::settle(g->ctx, rc);
-	return rc;
+	return kwage::settle(g->ctx, rc);
 }

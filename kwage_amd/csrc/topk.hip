@@ -5,8 +5,9 @@
 //               |->  count_kernel<SEG> + topk_combine_kernel (long queries)
 //
 // The batch layout, the k-mer stage, the counter widths, the segment rule and the result block are engine.hip's
-// (declared in engine_state.hpp), as are the host-side objects (context, group, batch); of kernels.hpp this unit
-// instantiates count_kernel's SEG form and the device functions topk_kernels.hpp builds on.
+// (declared in engine_state.hpp), as are the host-side objects (context, group, batch); the k-mer stage into blocks of
+// the call is pool_blocks.hpp's, the launches and the slice driver are tile_search.hpp's (shared with scores.hip).  Of
+// kernels.hpp this unit instantiates count_kernel's SEG form and the device functions topk_kernels.hpp builds on.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -23,67 +24,20 @@
 #include "pool_blocks.hpp"
 #include "kernels.hpp"
 #include "topk_kernels.hpp"
+#include "tile_search.hpp"
 
 namespace kwage {
 namespace {
 
-struct Events {
-	hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-	~Events() { for(hipEvent_t e : ev){ if(e){ (void)hipEventDestroy(e); } } }
+struct TopkKernels {
+	using Epi = TopkArgs;
+	static constexpr const char *tile_name = "topk_tile_kernel<%u,%u>+topk_merge_kernel";
+	static constexpr const char *seg_name = "count_kernel<%u,%u>+topk_combine_kernel<%u>+topk_merge_kernel";
+	template <int PLANES, int NH> static auto tile() { return topk_tile_kernel<PLANES, NH>; }
+	template <int PLANES> static auto combine() { return topk_combine_kernel<PLANES>; }      // (its grid is flat: any number of queries)
 };
 
-template <int PLANES, int NH>
-void launch_tile(const SearchArgs &a, const TopkArgs &t, hipStream_t s)
-{
-	const uint64_t tiles = (uint64_t)a.n_queries*a.chunks;
-	hipLaunchKernelGGL((topk_tile_kernel<PLANES, NH>), dim3((uint32_t)((tiles + 3)/4)), dim3(SEARCH_THREADS), 0, s, a, t);
-}
-
-template <int PLANES, int NH>
-void launch_seg_count(const SearchArgs &a, hipStream_t s)
-{
-	const uint64_t tiles = (uint64_t)a.n_queries*a.segs*a.chunks;
-	hipLaunchKernelGGL((count_kernel<PLANES, NH, true>), dim3((uint32_t)((tiles + 3)/4)), dim3(SEARCH_THREADS), 0, s, a);
-}
-
-template <int PLANES>
-int launch_combine(const SearchArgs &a, const TopkArgs &t, uint32_t seg_planes, hipStream_t s)
-{
-	const size_t lds = (size_t)(COMBINE_WAVES/2)*PLANES*WAVE*16;
-	if(lds > 48*1024){
-		HIP_TRY(hipFuncSetAttribute((const void*)topk_combine_kernel<PLANES>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-	}
-	hipLaunchKernelGGL((topk_combine_kernel<PLANES>), dim3(a.n_queries*a.chunks), dim3(COMBINE_WAVES*WAVE), lds, s, a, t, seg_planes);
-	return KWAGE_OK;
-}
-
-// dispatch on (planes, hash functions) as engine.hip's count path does
-template <template <int, int> class F, typename... A>
-void by_shape(uint32_t planes, uint32_t nh, A&&... args)
-{
-	auto go = [&](auto P) {
-		constexpr int PL = decltype(P)::value;
-		switch(nh){
-			case 1: F<PL, 1>::run(args...); break;
-			case 2: F<PL, 2>::run(args...); break;
-			case 3: F<PL, 3>::run(args...); break;
-			case 4: F<PL, 4>::run(args...); break;
-			default: F<PL, 5>::run(args...); break;
-		}
-	};
-	switch(planes){
-		case 7: go(std::integral_constant<int, 7>()); break;
-		case 10: go(std::integral_constant<int, 10>()); break;
-		case 14: go(std::integral_constant<int, 14>()); break;
-		case 20: go(std::integral_constant<int, 20>()); break;
-		default: go(std::integral_constant<int, 32>()); break;
-	}
-}
-template <int P, int NH> struct TileLaunch { static void run(const SearchArgs &a, const TopkArgs &t, hipStream_t s) { launch_tile<P, NH>(a, t, s); } };
-template <int P, int NH> struct SegLaunch { static void run(const SearchArgs &a, hipStream_t s) { launch_seg_count<P, NH>(a, s); } };
-
 static const uint64_t CAND_BYTES_PER_SLICE = 256ull << 20;     // candidate keys of one slice of the batch's queries
-static const uint64_t SLAB_BYTES_PER_SLICE = 1ull << 30;       // partial counters of one slice (segmented form)
 
 // What the selection stage leaves on the device: per query (batch order) the k-mer count, the floor and the number of
 // records selected, and up to k records per query in d_out[q*k ...], ordered by column (columns local to the group).
@@ -97,7 +51,7 @@ struct TopkSelection {
 
 // The selection stage of kwage_search_topk and kwage_search_topk_device_append: k-mer stage, tile kernels (or segments
 // + combine) and the per-query merge, queued on the context's first stream and not waited for.
-int topk_select(kwage_group *g, kwage_batch *b, uint32_t k, float threshold, uint32_t flags, PoolBlocks &blocks, Events &ev,
+int topk_select(kwage_group *g, kwage_batch *b, uint32_t k, float threshold, uint32_t flags, PoolBlocks &blocks, Events<4> &ev,
                 TopkSelection &sel)
 {
 	kwage_ctx *ctx = g->ctx;
@@ -105,114 +59,45 @@ int topk_select(kwage_group *g, kwage_batch *b, uint32_t k, float threshold, uin
 	if((rc = set_device(ctx))){ return rc; }
 	const KmerLayout *L = nullptr;
 	if((rc = batch_prepare(b, g->params.kmer_len, &L))){ return rc; }
-	const uint32_t nh = g->params.num_hash;
-	if(L->max_pos*nh > 0xFFFFFFFFull){
-		return fail(KWAGE_ERR_ARG, "a query of %llu k-mer positions x %u hash functions exceeds 2^32 rows", (unsigned long long)L->max_pos, nh);
-	}
 	hipStream_t s = ctx->stream;
 	const uint32_t n = b->n;
 	const bool timing = (flags & KWAGE_SEARCH_TIMING) != 0;
 	const bool timing_kmer = timing && (flags & KWAGE_SEARCH_TIMING_KMER);
-	if(timing){ for(hipEvent_t &e : ev.ev){ HIP_TRY(hipEventCreate(&e)); } }
-
-	uint32_t *d_rows = nullptr, *d_nkmer = nullptr, *d_qthr = nullptr, *d_out_n = nullptr;
-	unsigned long long *d_tables = nullptr, *d_missing = nullptr;
-	kwage_hit *d_out = nullptr;
-	if((rc = blocks.take(std::max<uint64_t>(L->total_pos*nh, 1)*sizeof(uint32_t), &d_rows))){ return rc; }
-	if((rc = blocks.take(std::max<uint64_t>(n, 1)*sizeof(uint32_t)*3 + 16, &d_nkmer))){ return rc; }
-	d_qthr = d_nkmer + std::max<uint32_t>(n, 1);
-	d_out_n = d_qthr + std::max<uint32_t>(n, 1);
-	d_missing = (unsigned long long*)(((uintptr_t)(d_out_n + std::max<uint32_t>(n, 1)) + 7) & ~(uintptr_t)7);
-	if((rc = blocks.take(std::max<uint64_t>((uint64_t)n*k, 1)*sizeof(kwage_hit), &d_out))){ return rc; }
-	HIP_TRY(hipMemsetAsync(d_missing, 0, sizeof(unsigned long long), s));
+	// the launches' shapes: a slice of the queries holds CAND_BYTES_PER_SLICE of candidate keys at most
+	const uint64_t cand_per_q = (uint64_t)tile_chunks(g)*k*sizeof(unsigned long long);
+	const bool any = n && g->num_columns;
+	TilePlan plan;
+	if((rc = plan_tiles(g, L->max_pos, any ? (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(n, CAND_BYTES_PER_SLICE/cand_per_q)) : 0, 0, &plan))){ return rc; }
+	if(timing && (rc = ev.create())){ return rc; }
 
 	// ---- k-mer stage: distinct canonical k-mers, row indices, the floor (unsigned)(t * n) of every query --------------
-	if(timing_kmer){ HIP_TRY(hipEventRecord(ev.ev[0], s)); }
-	if(n){
-		if(L->table_slots){
-			if((rc = blocks.take(L->table_slots*sizeof(uint64_t), &d_tables))){ return rc; }
-			HIP_TRY(hipMemsetAsync(d_tables, 0xFF, L->table_slots*sizeof(uint64_t), s));
-		}
-		// (the floor at t = 1 is n: no complete_match here.  kwage_search reports 0 there, its AND path has no floor)
-		const KmerStageOut o = {d_rows, nullptr, d_nkmer, d_qthr, d_tables};
-		if((rc = launch_kmer_kernels(g->params, b, L, threshold, 0, o, s))){ return rc; }
-		if(g->d_row_map && (rc = launch_remap_rows(g, n, L, d_rows, d_nkmer, d_missing, s))){ return rc; }
-	}
-	if(timing_kmer){ HIP_TRY(hipEventRecord(ev.ev[1], s)); }
+	// (the floor at t = 1 is n: no complete_match here.  kwage_search reports 0 there, its AND path has no floor)
+	KmerBlocks kb;
+	if((rc = kmer_prologue(g, b, L, threshold, true, true, timing_kmer ? ev.ev : nullptr, blocks, s, &kb))){ return rc; }
+	sel.d_nkmer = kb.nkmer;
+	sel.d_qthr = kb.qthr;
+	sel.d_out_n = kb.extra;
+	sel.d_missing = kb.missing;
+	if((rc = blocks.take(std::max<uint64_t>((uint64_t)n*k, 1)*sizeof(kwage_hit), &sel.d_out))){ return rc; }
 
 	// ---- selection: tile kernels (or segments + combine) and the per-query merge, slice by slice of the queries --------
-	char kernel_name[64] = "";
-	uint32_t launches = 0;
 	if(timing){ HIP_TRY(hipEventRecord(ev.ev[2], s)); }
-	if(n && g->num_columns){
-		SearchArgs a;
-		memset(&a, 0, sizeof(a));
-		a.db = g->d_bits;
-		a.stride = g->stride;
-		a.units_per_row = (uint32_t)(g->stride/16);
-		a.valid = g->d_valid;
-		a.rows = d_rows;
-		a.num_hash = nh;
-		a.chunks = (a.units_per_row + WAVE - 1)/WAVE;
-		const uint32_t planes = planes_for(L->max_pos);
-		const uint64_t cand_per_q = (uint64_t)a.chunks*k*sizeof(unsigned long long);
-		uint32_t slice = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(n, CAND_BYTES_PER_SLICE/cand_per_q));
-		a.n_queries = slice;
-		choose_segments(a, L->max_pos, 1024, ctx->tune.force_segs);      // (topk_combine_kernel's grid is flat: any number of queries)
-		uint32_t seg_planes = (a.segs > 1) ? planes_for(a.seg_kmers) : planes;
-		if(a.segs > 1){      // keep the slab of partial counters bounded: fewer queries per slice
-			const uint64_t slab_per_q = (uint64_t)a.segs*seg_planes*g->stride;
-			slice = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(slice, SLAB_BYTES_PER_SLICE/slab_per_q));
-		}
-		if((uint64_t)slice*a.segs*a.chunks/4 + 1 > 0x7FFFFFFFull){ return fail(KWAGE_ERR_ARG, "batch too large for one launch"); }
+	if(any){
 		TopkArgs t;
 		t.k = k;
-		t.tiles = a.chunks;
-		if((rc = blocks.take((uint64_t)slice*cand_per_q, &t.cand))){ return rc; }
-		if((rc = blocks.take((uint64_t)slice*a.chunks*sizeof(uint32_t), &t.cand_n))){ return rc; }
-		if(a.segs > 1){
-			uint32_t *slab = nullptr;
-			if((rc = blocks.take((uint64_t)slice*a.segs*seg_planes*g->stride, &slab))){ return rc; }
-			a.partial = slab;
-			snprintf(kernel_name, sizeof(kernel_name), "count_kernel<%u,%u>+topk_combine_kernel<%u>+topk_merge_kernel", seg_planes, std::min(nh, 5u), planes);
-		}
-		else{
-			snprintf(kernel_name, sizeof(kernel_name), "topk_tile_kernel<%u,%u>+topk_merge_kernel", planes, std::min(nh, 5u));
-		}
-		for(uint32_t q0 = 0; q0 < n; q0 += slice){
-			a.n_queries = std::min(slice, n - q0);
-			a.pos_off = L->d_pos_off + q0;
-			a.nkmer = d_nkmer + q0;
-			a.qthr = d_qthr + q0;
-			if(a.segs > 1){
-				by_shape<SegLaunch>(seg_planes, nh, a, s);
-				HIP_TRY(hipGetLastError());
-				switch(planes){
-					case 7: rc = launch_combine<7>(a, t, seg_planes, s); break;
-					case 10: rc = launch_combine<10>(a, t, seg_planes, s); break;
-					case 14: rc = launch_combine<14>(a, t, seg_planes, s); break;
-					case 20: rc = launch_combine<20>(a, t, seg_planes, s); break;
-					default: rc = launch_combine<32>(a, t, seg_planes, s); break;
-				}
-				if(rc){ return rc; }
-			}
-			else{
-				by_shape<TileLaunch>(planes, nh, a, t, s);
-			}
+		t.tiles = plan.chunks;
+		if((rc = blocks.take((uint64_t)plan.slice*cand_per_q, &t.cand))){ return rc; }
+		if((rc = blocks.take((uint64_t)plan.slice*plan.chunks*sizeof(uint32_t), &t.cand_n))){ return rc; }
+		const RowListView v = {kb.rows, L->d_pos_off, kb.nkmer, n, L->max_pos, g->params.num_hash};
+		rc = run_tile_slices<TopkKernels>(g, v, kb.qthr, plan, t, blocks, sel.kernel_name, s, [&](const SearchArgs &a, uint32_t q0) -> int {
+			hipLaunchKernelGGL(topk_merge_kernel, dim3(a.n_queries), dim3(MERGE_THREADS), 0, s, t, q0, sel.d_out + (uint64_t)q0*k, sel.d_out_n + q0);
 			HIP_TRY(hipGetLastError());
-			hipLaunchKernelGGL(topk_merge_kernel, dim3(a.n_queries), dim3(MERGE_THREADS), 0, s, t, q0, d_out + (uint64_t)q0*k, d_out_n + q0);
-			HIP_TRY(hipGetLastError());
-			++launches;
-		}
+			++sel.launches;
+			return KWAGE_OK;
+		});
+		if(rc){ return rc; }
 	}
 	if(timing){ HIP_TRY(hipEventRecord(ev.ev[3], s)); }
-	sel.d_nkmer = d_nkmer;
-	sel.d_qthr = d_qthr;
-	sel.d_out_n = d_out_n;
-	sel.d_missing = d_missing;
-	sel.d_out = d_out;
-	sel.launches = launches;
-	memcpy(sel.kernel_name, kernel_name, sizeof(sel.kernel_name));
 	return KWAGE_OK;
 }
 
@@ -229,7 +114,7 @@ int search_topk(kwage_group *g, kwage_batch *b, uint32_t k, float threshold, uin
 {
 	int rc;
 	if((rc = topk_check(g, b, k, threshold, "kwage_search_topk"))){ return rc; }
-	Events ev;
+	Events<4> ev;
 	TopkSelection sel;
 	if((rc = topk_select(g, b, k, threshold, flags, blocks, ev, sel))){ return rc; }
 	kwage_ctx *ctx = g->ctx;
@@ -261,9 +146,7 @@ int search_topk(kwage_group *g, kwage_batch *b, uint32_t k, float threshold, uin
 		HIP_TRY(hipMemcpyAsync(&missing, d_missing, sizeof(missing), hipMemcpyDeviceToHost, s));
 	}
 	HIP_TRY(hipStreamSynchronize(s));
-	if(missing){
-		return fail(KWAGE_ERR_STATE, "%llu row indices of this batch are not among the rows of the sparse group (it was created for other queries)", missing);
-	}
+	if(missing){ return fail_missing_rows(missing); }
 	uint64_t n_hits = 0, total_kmers = 0;
 	for(uint32_t q = 0; q < n; ++q){ n_hits += std::min(out_n[q], k); total_kmers += rs->nkmer[q]; }
 	rs->hits.reset(new (std::nothrow) kwage_hit[std::max<uint64_t>(n_hits, 1)]);
@@ -303,7 +186,7 @@ int search_topk_device_append(kwage_group *g, kwage_batch *b, uint32_t k, float 
 	if((uint64_t)column_base + g->stride*8 > 0x100000000ull){
 		return fail(KWAGE_ERR_ARG, "kwage_search_topk_device_append: column base %u + the group's column span exceeds 32 bits", column_base);
 	}
-	Events ev;
+	Events<4> ev;
 	TopkSelection sel;
 	if((rc = topk_select(g, b, k, threshold, flags & ~(uint32_t)(KWAGE_SEARCH_TIMING | KWAGE_SEARCH_TIMING_KMER), blocks, ev, sel))){ return rc; }
 	hipStream_t s = g->ctx->stream;
@@ -314,9 +197,7 @@ int search_topk_device_append(kwage_group *g, kwage_batch *b, uint32_t k, float 
 	HIP_TRY(hipMemcpyAsync(&missing, sel.d_missing, sizeof(missing), hipMemcpyDeviceToHost, s));
 	if(!reset_count){ HIP_TRY(hipMemcpyAsync(&base, count_dev, sizeof(base), hipMemcpyDeviceToHost, s)); }
 	HIP_TRY(hipStreamSynchronize(s));
-	if(missing){
-		return fail(KWAGE_ERR_STATE, "%llu row indices of this batch are not among the rows of the sparse group (it was created for other queries)", missing);
-	}
+	if(missing){ return fail_missing_rows(missing); }
 	// the output offsets of the queries, in batch order: the list grows by query, then column, behind what it held
 	std::vector<unsigned long long> off(std::max<uint32_t>(n, 1), 0);
 	unsigned long long added = 0;
@@ -347,14 +228,7 @@ extern "C" int kwage_search_topk(kwage_group *g, kwage_batch *b, uint32_t k, flo
 	if(!g || !b || !out){ return kwage::fail(KWAGE_ERR_ARG, "kwage_search_topk: NULL argument"); }
 	*out = nullptr;
 	kwage::PoolBlocks blocks(&g->ctx->batch_pool);
-	const int rc = kwage::search_topk(g, b, k, threshold, flags, blocks, out);
-	if(rc){
-		// an error return may leave kernels of this call queued: nothing of it may still run when `blocks` hands its
-		// device memory back to the pool (its destructor, below)
-		(void)hipStreamSynchronize(g->ctx->stream);
-		(void)hipGetLastError();
-	}
-	return rc;
+	return kwage::settle(g->ctx, kwage::search_topk(g, b, k, threshold, flags, blocks, out));
 }
 
 extern "C" int kwage_search_topk_device_append(kwage_group *g, kwage_batch *b, uint32_t k, float threshold, uint32_t flags,
@@ -365,11 +239,6 @@ extern "C" int kwage_search_topk_device_append(kwage_group *g, kwage_batch *b, u
 		return kwage::fail(KWAGE_ERR_ARG, "kwage_search_topk_device_append: NULL argument");
 	}
 	kwage::PoolBlocks blocks(&g->ctx->batch_pool);
-	const int rc = kwage::search_topk_device_append(g, b, k, threshold, flags, hits_dev, capacity, count_dev, column_base,
-	                                                reset_count, num_query_kmer_dev, blocks, n_total);
-	if(rc){      // as kwage_search_topk: nothing of this call may still run when `blocks` hands its memory back
-		(void)hipStreamSynchronize(g->ctx->stream);
-		(void)hipGetLastError();
-	}
-	return rc;
+	return kwage::settle(g->ctx, kwage::search_topk_device_append(g, b, k, threshold, flags, hits_dev, capacity, count_dev, column_base,
+	                                                              reset_count, num_query_kmer_dev, blocks, n_total));
 }

@@ -108,11 +108,6 @@ extern "C" int kwage_topk_merge_device(kwage_ctx *ctx, const void *hits_dev, uin
 		return kwage::fail(KWAGE_ERR_ARG, "kwage_topk_merge_device: NULL argument");
 	}
 	kwage::PoolBlocks blocks(&ctx->batch_pool);
-	const int rc = kwage::topk_merge(ctx, hits_dev, n_hits, n_queries, k, order_dev, n_order, out_dev, out_capacity,
-	                                 out_count_dev, blocks);
-	if(rc){      // nothing of this call may still run when `blocks` hands its memory back to the pool
-		(void)hipStreamSynchronize(ctx->stream);
-		(void)hipGetLastError();
-	}
-	return rc;
+	return kwage::settle(ctx, kwage::topk_merge(ctx, hits_dev, n_hits, n_queries, k, order_dev, n_order, out_dev, out_capacity,
+	                                            out_count_dev, blocks));
 }
