@@ -303,6 +303,36 @@ int kwage_search_scores(kwage_group *g, kwage_batch *b, uint32_t *scores, uint64
  * "score_tile_kernel<10,1>", "count_kernel<7,1>+score_combine_kernel<14>"; "" if none.  Valid until the thread's next one. */
 const char *kwage_search_scores_kernel(void);
 
+/* Presence search, no counterpart in the reference: one pass/fail bit per (query, column), the matrix a BIGSI-style
+ * index answers with.  Query q has n distinct k-mers and the floor f = kwage_query_threshold(threshold, n) (n at t = 1);
+ * bit (q, c) is 1 iff n > 0, c is a real column and the column's num_match >= f: exactly the (q, c) for which
+ * kwage_search(g, b, threshold, ...) returns a record, for every 0 < t <= 1 and n < 2^24.  With floor 0 every real
+ * column of a query that has k-mers passes.  Pad bits are 0; the row of a query without k-mers is 0.
+ *   - bit (q, c) lies at bits[q*row_bytes + c/8], bit c%8 (LSB first): the layout of a row of the resident matrix;
+ *   - with W = kwage_group_row_bytes(g) rounded up to 16: row_bytes >= W and row_bytes % 16 == 0; bits_dev is 16-byte
+ *     aligned.  Bytes [0, W) of every row are written (nothing has to be cleared beforehand), bytes at or beyond W
+ *     are not touched;
+ *   - passing / passing_dev may be NULL or receive n_queries uint32: the set bits of each query's row;
+ *   - num_query_kmer / num_query_kmer_dev may be NULL or hold n_queries uint32 (host / device memory);
+ *   - KWAGE_SEARCH_TIMING fills *search_kernel_ms (may be NULL) with the HIP-event duration of the presence kernels;
+ *     KWAGE_SEARCH_EARLY_EXIT lets a (query, KiB tile) in which no column can pass any more stop and store its zeros:
+ *     the bitmap is bit for bit the same with and without it (the segmented form of few long queries ignores it).
+ * Errors of two kinds.  Found on the host before any kernel is launched: KWAGE_ERR_STATE before kwage_group_finalize;
+ * KWAGE_ERR_ARG for mixed contexts, a wrong row_bytes, a misaligned or NULL pointer, a threshold outside [0, 1] (NaN
+ * included), a query of 2^32 rows and more, or a batch too large for one launch.  Found on the device: KWAGE_ERR_STATE
+ * for a sparse group whose row list does not cover the batch, known once the k-mer stage has computed the batch's rows
+ * and before the first presence kernel.  In either kind nothing of the caller's memory is written.
+ * Synchronous; runs on the context's first stream; device scratch comes from the context's pool.
+ * kwage_search_presence is the same search with the bitmap copied to host memory. */
+int kwage_search_presence_device(kwage_group *g, kwage_batch *b, float threshold, void *bits_dev, uint64_t row_bytes,
+                                 void *passing_dev, void *num_query_kmer_dev, uint32_t flags, float *search_kernel_ms);
+int kwage_search_presence(kwage_group *g, kwage_batch *b, float threshold, uint8_t *bits, uint64_t row_bytes,
+                          uint32_t *passing, uint32_t *num_query_kmer, uint32_t flags, float *search_kernel_ms);
+/* Which kernels the calling thread's last presence search launched, with their template shapes:
+ * "presence_tile_kernel<10,1>", "count_kernel<7,1>+presence_combine_kernel<14>", "presence_and_kernel"; "" if none.
+ * Valid until the thread's next one. */
+const char *kwage_search_presence_kernel(void);
+
 /* Filter set, no counterpart in the reference: n whole Bloom filters over 2^L rows as the QUESTIONS of a search ("which
  * samples look like this sample").  On the device a set is one concatenated uint32 row list -- the rows in which each
  * filter is set, ascending -- with a uint64 prefix array of n + 1 entries and each filter's set-bit count: the shape a

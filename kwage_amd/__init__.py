@@ -9,9 +9,10 @@ from .native import KwageError, lib, lib_path, build_native   # noqa: F401
 from .engine import (Context, Group, Batch, Database, FileDatabase, DatabaseHit, SearchResult, PendingSearch, Params, hash_batch,   # noqa: F401
                      search_topk, search_topk_device_append, merge_topk_device, TOPK_MAX,
                      ScoreResult, search_scores, search_scores_device,
+                     PresenceResult, search_presence, search_presence_device,
                      FilterSet, search_filter_scores, search_filter_scores_device,
                      SEARCH_EARLY_EXIT, SEARCH_TIMING, SEARCH_TIMING_KMER)
 
 __all__ = ["KwageError", "lib", "lib_path", "build_native", "Context", "Group", "Batch", "Database", "FileDatabase", "DatabaseHit",
            "SearchResult", "PendingSearch", "Params", "hash_batch", "search_topk",
-           "search_topk_device_append", "merge_topk_device", "TOPK_MAX", "ScoreResult", "search_scores", "search_scores_device", "FilterSet", "search_filter_scores", "search_filter_scores_device", "SEARCH_EARLY_EXIT", "SEARCH_TIMING", "SEARCH_TIMING_KMER"]
+           "search_topk_device_append", "merge_topk_device", "TOPK_MAX", "ScoreResult", "search_scores", "search_scores_device", "PresenceResult", "search_presence", "search_presence_device", "FilterSet", "search_filter_scores", "search_filter_scores_device", "SEARCH_EARLY_EXIT", "SEARCH_TIMING", "SEARCH_TIMING_KMER"]

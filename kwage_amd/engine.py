@@ -410,6 +410,61 @@ def search_scores_device(group: Group, batch: Batch, out, num_query_kmer=None, f
     return ScoreResult(out, num_query_kmer, (lib().kwage_search_scores_kernel() or b"").decode(), float(ms.value))
 
 
+@dataclass
+class PresenceResult:
+    bits: object                     # uint8 [n, row_bytes] numpy array (search_presence) / the caller's device tensor (search_presence_device)
+    passing: object                  # uint32 per query: the set bits of its row; None (search_presence_device without the tensor)
+    num_query_kmer: object           # uint32 per query, or None (search_presence_device without the tensor)
+    kernel: str                      # "presence_tile_kernel<10,1>", "count_kernel<7,1>+presence_combine_kernel<14>", "presence_and_kernel", "" if nothing ran
+    kernel_ms: float                 # with SEARCH_TIMING, else 0
+
+    def unpack(self) -> np.ndarray:
+        """bool [n, column span]: cell (q, c) = bit c of row q (host results)."""
+        bits = np.ascontiguousarray(self.bits)
+        return np.unpackbits(bits, axis=1, bitorder="little").astype(bool) if bits.size else np.zeros((bits.shape[0], bits.shape[1] * 8), dtype=bool)
+
+
+def presence_row_bytes(group: Group) -> int:
+    """The bytes of a row that a presence search writes: the group's row bytes rounded up to 16."""
+    return (group.row_bytes + 15) // 16 * 16
+
+
+def search_presence(group: Group, batch: Batch, threshold: float, flags: int = 0) -> PresenceResult:
+    """kwage_search_presence(): one bit per (query, column) of the group, set where kwage_search at the same threshold
+    reports a record, as a uint8 [n, row_bytes] matrix in the byte order of the group's rows (pad bits and queries
+    without k-mers: 0)."""
+    n, w = batch.n, presence_row_bytes(group)
+    buf = np.zeros((n, w), dtype=np.uint8)
+    passing = np.zeros(max(n, 1), dtype=np.uint32)
+    nk = np.zeros(max(n, 1), dtype=np.uint32)
+    ms = C.c_float(0)
+    check(lib().kwage_search_presence(group._h, batch._h, C.c_float(threshold), buf.ctypes.data if buf.size else None, w, passing.ctypes.data,
+                                      nk.ctypes.data, flags, C.byref(ms)))
+    return PresenceResult(buf[:, :group.row_bytes], passing[:n], nk[:n], (lib().kwage_search_presence_kernel() or b"").decode(), float(ms.value))
+
+
+def search_presence_device(group: Group, batch: Batch, threshold: float, out, passing=None, num_query_kmer=None, flags: int = 0) -> PresenceResult:
+    """kwage_search_presence_device(): the same bitmap written into `out`, a uint8 device tensor [n, >= W] (W: the
+    group's row bytes rounded up to 16) with unit inner stride, rows a multiple of 16 bytes apart and a 16-byte aligned
+    first byte (a block of columns of a wider matrix will do); bytes of `out` at or beyond W are left alone.  passing,
+    num_query_kmer: None or int32 [n] device tensors."""
+    import torch
+    _device_tensor(out, "out", torch.uint8, row_multiple=16)
+    w = presence_row_bytes(group)
+    if out.dim() != 2 or out.shape[0] != batch.n or out.shape[1] < w:
+        raise ValueError("out: shape [%d, >= %d] required, got %s" % (batch.n, w, tuple(out.shape)))
+    row_bytes = out.stride(0) if out.shape[0] > 1 else w         # (a single row: the distance between rows addresses nothing)
+    ptrs = []
+    for t, name in ((passing, "passing"), (num_query_kmer, "num_query_kmer")):
+        if t is not None and _device_tensor(t, name, torch.int32).numel() < batch.n:
+            raise ValueError("%s: %d elements required" % (name, batch.n))
+        ptrs.append(t.data_ptr() if t is not None else 0)
+    ms = C.c_float(0)
+    check(lib().kwage_search_presence_device(group._h, batch._h, C.c_float(threshold), out.data_ptr() or None, row_bytes, ptrs[0] or None,
+                                             ptrs[1] or None, flags, C.byref(ms)))
+    return PresenceResult(out, passing, num_query_kmer, (lib().kwage_search_presence_kernel() or b"").decode(), float(ms.value))
+
+
 class FilterSet:
     """Whole Bloom filters as the questions of a search (kwage_filterset): their set rows as ascending row lists on the
     device.  Belongs to its context; close() it before the context."""
@@ -514,6 +569,7 @@ Group.search = lambda self, batch, threshold, flags=0: search(self, batch, thres
 Group.search_topk = lambda self, batch, k, threshold=0.0, flags=0: search_topk(self, batch, k, threshold, flags)
 Group.submit = lambda self, batch, threshold, flags=0: submit(self, batch, threshold, flags)
 Group.search_scores = lambda self, batch, flags=0: search_scores(self, batch, flags)
+Group.search_presence = lambda self, batch, threshold, flags=0: search_presence(self, batch, threshold, flags)
 Group.search_filter_scores = lambda self, fs, flags=0: search_filter_scores(self, fs, flags)
 
 
@@ -605,6 +661,27 @@ class Database:
             if batch.n and g.column_span:
                 search_scores_device(g, batch, out[:, base:base + g.column_span])
         return out
+
+    def search_presence(self, batch: Batch, threshold: float, flags: int = 0):
+        """Which columns of the whole database hold each query at the threshold: (uint8 device tensor [n, sum of the
+        groups' W], bit bases) in a single allocation, W a group's row bytes rounded up to 16.  Each group's block
+        starts at a 16-byte aligned byte of the row (the column bases of the score and top-k forms are multiples of 8
+        columns only, too little for the kernels' 16-byte stores), so this form numbers the columns itself: column c of
+        group i is bit bases[i] + c of a row, byte (bases[i] + c) // 8, bit (bases[i] + c) % 8.  Pad bits hold 0."""
+        import torch
+        if not self.groups:
+            raise ValueError("Database.search_presence: no groups")
+        dev = torch.device("cuda", self.groups[0].ctx.device)
+        bases, at = [], 0
+        for g in self.groups:
+            bases.append(at * 8)
+            at += presence_row_bytes(g)
+        out = torch.empty((batch.n, at), dtype=torch.uint8, device=dev)
+        for g, base in zip(self.groups, bases):
+            w = presence_row_bytes(g)
+            if batch.n and w:
+                search_presence_device(g, batch, threshold, out[:, base // 8:base // 8 + w], flags=flags)
+        return out, bases
 
     def similar(self, fs: "FilterSet", k: int) -> List[List[Tuple[int, int, int, int, int, float]]]:
         """Per filter of the set, the k samples of the database most like it by Jaccard index: the filter search of every
@@ -772,6 +849,27 @@ class FileDatabase(Database):
             full = self.search_scores(b).cpu().numpy().view(np.uint32) if self.groups else np.zeros((b.n, 0), np.uint32)
         finally:
             b.close()
+        return np.ascontiguousarray(full[:, cols]), accessions
+
+    def presence_matrix(self, seqs: Sequence[bytes | str], threshold: float = 1.0) -> Tuple[np.ndarray, List[str]]:
+        """What `kwage_presence -t <threshold> -d ... <seqs>` prints, as (bool [n_queries, n_samples], run accessions):
+        the real columns only, in file order then column order."""
+        cols, accessions = [], []
+        b = Batch(self.ctx, seqs)
+        try:
+            if self.groups:
+                packed, bases = self.search_presence(b, threshold)
+                full = np.unpackbits(packed.cpu().numpy(), axis=1, bitorder="little").astype(bool)
+            else:
+                full, bases = np.zeros((b.n, 0), dtype=bool), []
+        finally:
+            b.close()
+        where = {path: (base, first, nf) for base, layout in zip(bases, self._layout) for first, nf, path in layout}
+        for f in self.files:
+            base, first, nf = where[f]
+            cols.append(int(base) + first + np.arange(nf, dtype=np.int64))
+            accessions.extend(self._accession(f, c) for c in range(nf))
+        cols = np.concatenate(cols) if cols else np.zeros(0, np.int64)
         return np.ascontiguousarray(full[:, cols]), accessions
 
     def similar_samples(self, accessions: Sequence[str], k: int) -> List[Tuple[str, List[Tuple[str, str, int, int, int, int, float]]]]:

@@ -14,6 +14,7 @@ KWAGE_TOP_BIN = os.path.join(_HERE, "bin", "kwage_top")
 KWAGE_TOP_NODE_BIN = os.path.join(_HERE, "bin", "kwage_top_node")
 KWAGE_SCORES_BIN = os.path.join(_HERE, "bin", "kwage_scores")
 KWAGE_NEAR_BIN = os.path.join(_HERE, "bin", "kwage_near")
+KWAGE_PRESENCE_BIN = os.path.join(_HERE, "bin", "kwage_presence")
 TOPK_MAX = 1024              # KWAGE_TOPK_MAX
 
 
@@ -47,7 +48,7 @@ def build_native(force: bool = False) -> str:
 def ensure_built() -> str:
     """Build the native library + CLI if (and only if) they are missing.  Used by bench.py / smoke();
     compiling the HIP extension is not a fallback -- nothing runs without it."""
-    if not all(os.path.exists(p) for p in (_LIB, KWAGE_BIN, KWAGE_TOP_BIN, KWAGE_SCORES_BIN, KWAGE_NEAR_BIN, KWAGE_DBTOOL_BIN)):
+    if not all(os.path.exists(p) for p in (_LIB, KWAGE_BIN, KWAGE_TOP_BIN, KWAGE_SCORES_BIN, KWAGE_PRESENCE_BIN, KWAGE_NEAR_BIN, KWAGE_DBTOOL_BIN)):
         build_native()
     return _LIB
 
@@ -142,6 +143,9 @@ _SIGNATURES = [
     ("kwage_search_scores_device", C.c_int, [_P, _P, _P, C.c_uint64, _P, C.c_uint32, C.POINTER(C.c_float)]),
     ("kwage_search_scores", C.c_int, [_P, _P, _P, C.c_uint64, _P, C.c_uint32, C.POINTER(C.c_float)]),
     ("kwage_search_scores_kernel", C.c_char_p, []),
+    ("kwage_search_presence_device", C.c_int, [_P, _P, C.c_float, _P, C.c_uint64, _P, _P, C.c_uint32, C.POINTER(C.c_float)]),
+    ("kwage_search_presence", C.c_int, [_P, _P, C.c_float, _P, C.c_uint64, _P, _P, C.c_uint32, C.POINTER(C.c_float)]),
+    ("kwage_search_presence_kernel", C.c_char_p, []),
     ("kwage_filterset_from_columns", C.c_int, [_P, _P, C.c_uint32, C.POINTER(_P)]),
     ("kwage_filterset_from_bits", C.c_int, [_P, C.POINTER(Params), _P, C.c_uint64, C.c_uint32, C.POINTER(_P)]),
     ("kwage_filterset_destroy", None, [_P]),
