@@ -542,85 +542,53 @@ void launch_and_v(const SearchArgs &a, hipStream_t s, const AndCfg &c, const Sta
 	else{ launch_and<4>(a, s, c, ge); }
 }
 
-template <int PLANES, int NH>
-void launch_count(const SearchArgs &a, hipStream_t s, const StageEvents &ge)
+// count_kernel with `planes` counter planes over the launch's tiles
+void launch_count(uint32_t planes, const SearchArgs &a, hipStream_t s, const StageEvents &ge)
 {
-	if(a.segs > 1){
-		KW_GATHER_LAUNCH(ge, true, false, (count_kernel<PLANES, NH, true>), dim3(search_blocks(a)), dim3(SEARCH_THREADS), 0, s, a);      // (count_combine_kernel ends the stage)
-	}
-	else{
-		KW_GATHER_LAUNCH(ge, true, true, (count_kernel<PLANES, NH, false>), dim3(search_blocks(a)), dim3(SEARCH_THREADS), 0, s, a);
-	}
+	by_shape(planes, a.num_hash, [&](auto P, auto NH) {
+		constexpr int PLANES = decltype(P)::value, H = decltype(NH)::value;
+		if(a.segs > 1){
+			KW_GATHER_LAUNCH(ge, true, false, (count_kernel<PLANES, H, true>), dim3(search_blocks(a)), dim3(SEARCH_THREADS), 0, s, a);      // (count_combine_kernel ends the stage)
+		}
+		else{
+			KW_GATHER_LAUNCH(ge, true, true, (count_kernel<PLANES, H, false>), dim3(search_blocks(a)), dim3(SEARCH_THREADS), 0, s, a);
+		}
+	});
 }
 
-template <int PLANES, int G>
-void launch_count_narrow(const SearchArgs &a, hipStream_t s, const StageEvents &ge)
+// count_narrow_kernel and count_screen_kernel exist for 7, 10 and 14 planes only (their callers have seen planes <= 14)
+template <typename F>
+void by_planes_to_14(uint32_t planes, F &&f)
+{
+	if(planes == 7){ f(std::integral_constant<int, 7>()); }
+	else if(planes == 10){ f(std::integral_constant<int, 10>()); }
+	else{ f(std::integral_constant<int, 14>()); }
+}
+
+// G queries per wave
+template <int G>
+void launch_count_narrow(uint32_t planes, const SearchArgs &a, hipStream_t s, const StageEvents &ge)
 {
 	const uint64_t waves = ((uint64_t)a.n_queries + G - 1)/G;
 	const dim3 grid((uint32_t)((waves + 3)/4)), block(SEARCH_THREADS);
-	switch(a.num_hash){
-		case 1: KW_GATHER_LAUNCH(ge, true, true, (count_narrow_kernel<PLANES, 1, G>), grid, block, 0, s, a); break;
-		case 2: KW_GATHER_LAUNCH(ge, true, true, (count_narrow_kernel<PLANES, 2, G>), grid, block, 0, s, a); break;
-		case 3: KW_GATHER_LAUNCH(ge, true, true, (count_narrow_kernel<PLANES, 3, G>), grid, block, 0, s, a); break;
-		case 4: KW_GATHER_LAUNCH(ge, true, true, (count_narrow_kernel<PLANES, 4, G>), grid, block, 0, s, a); break;
-		default: KW_GATHER_LAUNCH(ge, true, true, (count_narrow_kernel<PLANES, 5, G>), grid, block, 0, s, a); break;
-	}
-}
-
-template <int PLANES>
-void launch_count_nh(const SearchArgs &a, hipStream_t s, const StageEvents &ge)
-{
-	switch(a.num_hash){
-		case 1: launch_count<PLANES, 1>(a, s, ge); break;
-		case 2: launch_count<PLANES, 2>(a, s, ge); break;
-		case 3: launch_count<PLANES, 3>(a, s, ge); break;
-		case 4: launch_count<PLANES, 4>(a, s, ge); break;
-		default: launch_count<PLANES, 5>(a, s, ge); break;
-	}
-}
-
-void launch_count_planes(uint32_t planes, const SearchArgs &a, hipStream_t s, const StageEvents &ge)
-{
-	switch(planes){
-		case 7: launch_count_nh<7>(a, s, ge); break;
-		case 10: launch_count_nh<10>(a, s, ge); break;
-		case 14: launch_count_nh<14>(a, s, ge); break;
-		case 20: launch_count_nh<20>(a, s, ge); break;
-		default: launch_count_nh<32>(a, s, ge); break;
-	}
-}
-
-template <int PLANES, int NH, bool TRUNC>
-void launch_count_walk(const SearchArgs &a, const CountWalkArgs &wa, const RefineArgs &ra, const WalkShape &w, hipStream_t s, const StageEvents &ge)
-{
-	if(w.lds > 48*1024){ (void)hipFuncSetAttribute((const void*)count_walk_kernel<PLANES, NH, TRUNC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)w.lds); }
-	// (TRUNC: the refine and emit launches end the stage)
-	KW_GATHER_LAUNCH(ge, true, !TRUNC, (count_walk_kernel<PLANES, NH, TRUNC>), dim3(w.wgs), dim3(w.wg_waves*WAVE), w.lds, s, a, wa, ra, a.rows, a.pos_off, a.nkmer, a.qthr);
-}
-
-template <int PLANES, bool TRUNC>
-void launch_count_walk_nh(const SearchArgs &a, const CountWalkArgs &wa, const RefineArgs &ra, const WalkShape &w, hipStream_t s, const StageEvents &ge)
-{
-	switch(a.num_hash){
-		case 1: launch_count_walk<PLANES, 1, TRUNC>(a, wa, ra, w, s, ge); break;
-		case 2: launch_count_walk<PLANES, 2, TRUNC>(a, wa, ra, w, s, ge); break;
-		case 3: launch_count_walk<PLANES, 3, TRUNC>(a, wa, ra, w, s, ge); break;
-		case 4: launch_count_walk<PLANES, 4, TRUNC>(a, wa, ra, w, s, ge); break;
-		default: launch_count_walk<PLANES, 5, TRUNC>(a, wa, ra, w, s, ge); break;
-	}
+	by_planes_to_14(planes, [&](auto P) {
+		by_nh(a.num_hash, [&](auto NH) {
+			KW_GATHER_LAUNCH(ge, true, true, (count_narrow_kernel<decltype(P)::value, decltype(NH)::value, G>), grid, block, 0, s, a);
+		});
+	});
 }
 
 template <bool TRUNC>
-void launch_count_walk_planes(uint32_t planes, const SearchArgs &a, const CountWalkArgs &wa, const RefineArgs &ra, const WalkShape &w, hipStream_t s, const StageEvents &ge)
+void launch_count_walk(uint32_t planes, const SearchArgs &a, const CountWalkArgs &wa, const RefineArgs &ra, const WalkShape &w, hipStream_t s, const StageEvents &ge)
 {
-	switch(planes){
+	by_shape(planes, a.num_hash, [&](auto P, auto NH) {
 		// (the truncated form counts a query of up to 127 k-mers with ten planes: the caller sizes slab and lists for that)
-		case 7: launch_count_walk_nh<TRUNC ? 10 : 7, TRUNC>(a, wa, ra, w, s, ge); break;
-		case 10: launch_count_walk_nh<10, TRUNC>(a, wa, ra, w, s, ge); break;
-		case 14: launch_count_walk_nh<14, TRUNC>(a, wa, ra, w, s, ge); break;
-		case 20: launch_count_walk_nh<20, TRUNC>(a, wa, ra, w, s, ge); break;
-		default: launch_count_walk_nh<32, TRUNC>(a, wa, ra, w, s, ge); break;
-	}
+		constexpr int PLANES = (TRUNC && decltype(P)::value == 7) ? 10 : decltype(P)::value;
+		const auto kernel = count_walk_kernel<PLANES, decltype(NH)::value, TRUNC>;
+		if(w.lds > 48*1024){ (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)w.lds); }
+		// (TRUNC: the refine and emit launches end the stage)
+		KW_GATHER_LAUNCH(ge, true, !TRUNC, kernel, dim3(w.wgs), dim3(w.wg_waves*WAVE), w.lds, s, a, wa, ra, a.rows, a.pos_off, a.nkmer, a.qthr);
+	});
 }
 
 struct RefineSetup { RefineArgs ra; uint32_t refine_wgs, emit_wgs; };
@@ -638,25 +606,28 @@ int check_refine_units(uint32_t planes, int up)
 void launch_count_refine_and_emit(uint32_t planes, int up, const SearchArgs &a, const RefineSetup &rs, hipStream_t gs, const StageEvents &ge)
 {
 	const dim3 block(SEARCH_THREADS);
-#define KWAGE_CR_NH(N) case N: if(up == 7){ KW_GATHER_LAUNCH(ge, false, false, (count_refine_kernel<N, 7>), dim3(rs.refine_wgs), block, 0, gs, a, rs.ra); } \
-		else{ KW_GATHER_LAUNCH(ge, false, false, (count_refine_kernel<N, 14>), dim3(rs.refine_wgs), block, 0, gs, a, rs.ra); } break;
-	switch(std::min(a.num_hash, 5u)){ KWAGE_CR_NH(1) KWAGE_CR_NH(2) KWAGE_CR_NH(3) KWAGE_CR_NH(4) default: KWAGE_CR_NH(5) }
-#undef KWAGE_CR_NH
-#define KWAGE_CE_P(P) case P: if(up == 7){ KW_GATHER_LAUNCH(ge, false, true, (count_refine_emit_kernel<P, 7>), dim3(rs.emit_wgs), block, 0, gs, a, rs.ra); } \
-		else{ KW_GATHER_LAUNCH(ge, false, true, (count_refine_emit_kernel<P, (P >= 14 ? 14 : 7)>), dim3(rs.emit_wgs), block, 0, gs, a, rs.ra); } break;
-	switch(planes){ KWAGE_CE_P(7) KWAGE_CE_P(10) KWAGE_CE_P(14) KWAGE_CE_P(20) default: KWAGE_CE_P(32) }
-#undef KWAGE_CE_P
+	by_nh(a.num_hash, [&](auto NH) {
+		constexpr int H = decltype(NH)::value;
+		if(up == 7){ KW_GATHER_LAUNCH(ge, false, false, (count_refine_kernel<H, 7>), dim3(rs.refine_wgs), block, 0, gs, a, rs.ra); }
+		else{ KW_GATHER_LAUNCH(ge, false, false, (count_refine_kernel<H, 14>), dim3(rs.refine_wgs), block, 0, gs, a, rs.ra); }
+	});
+	by_planes(planes, [&](auto P) {
+		constexpr int PLANES = decltype(P)::value, UP14 = (PLANES >= 14) ? 14 : 7;      // (<P, 14> exists for P >= 14 only: check_refine_units)
+		if(up == 7){ KW_GATHER_LAUNCH(ge, false, true, (count_refine_emit_kernel<PLANES, 7>), dim3(rs.emit_wgs), block, 0, gs, a, rs.ra); }
+		else{ KW_GATHER_LAUNCH(ge, false, true, (count_refine_emit_kernel<PLANES, UP14>), dim3(rs.emit_wgs), block, 0, gs, a, rs.ra); }
+	});
 }
 
-template <int PLANES>
-int launch_count_combine(const SearchArgs &a, uint32_t seg_planes, hipStream_t s, const StageEvents &ge)
+int launch_count_combine(uint32_t planes, const SearchArgs &a, uint32_t seg_planes, hipStream_t s, const StageEvents &ge)
 {
-	const size_t lds = (size_t)(COMBINE_WAVES/2)*PLANES*WAVE*16;
-	if(lds > 48*1024){      // 32 planes only (queries above 2^20 positions); the attribute is per device, so set it per launch
-		HIP_TRY(hipFuncSetAttribute((const void*)count_combine_kernel<PLANES>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-	}
-	KW_GATHER_LAUNCH(ge, false, true, (count_combine_kernel<PLANES>), dim3((a.units_per_row + WAVE - 1)/WAVE, a.n_queries), dim3(COMBINE_WAVES*WAVE), lds, s, a, seg_planes);
-	return KWAGE_OK;
+	return by_planes(planes, [&](auto P) -> int {
+		constexpr int PLANES = decltype(P)::value;
+		constexpr size_t lds = (size_t)(COMBINE_WAVES/2)*PLANES*WAVE*16;
+		int rc;
+		if((rc = allow_dynamic_lds(count_combine_kernel<PLANES>, lds))){ return rc; }
+		KW_GATHER_LAUNCH(ge, false, true, (count_combine_kernel<PLANES>), dim3((a.units_per_row + WAVE - 1)/WAVE, a.n_queries), dim3(COMBINE_WAVES*WAVE), lds, s, a, seg_planes);
+		return KWAGE_OK;
+	});
 }
 
 // The segment limit of a launch of this search: its combine kernels index queries with gridDim.y, so no segments above
@@ -986,11 +957,11 @@ int launch_search_stage(Slot *sl, kwage_group *g, kwage_batch *b, const KmerLayo
 			a.segs = 1;
 			snprintf(sl->kernel_name, sizeof(sl->kernel_name), "count_screen_kernel<%u,%u>+refine<%d>", planes, std::min(a.num_hash, 5u), up);
 			const dim3 grid((uint32_t)(screen_waves/4)), block(SEARCH_THREADS);
-#define KWAGE_CS_NH(P, N) case N: KW_GATHER_LAUNCH(ge, true, false, (count_screen_kernel<P, N>), grid, block, 0, gs, a, rs.ra); break;
-#define KWAGE_CS_P(P) case P: switch(std::min(a.num_hash, 5u)){ KWAGE_CS_NH(P, 1) KWAGE_CS_NH(P, 2) KWAGE_CS_NH(P, 3) KWAGE_CS_NH(P, 4) default: KWAGE_CS_NH(P, 5) } break;
-			switch(planes){ KWAGE_CS_P(7) KWAGE_CS_P(10) default: KWAGE_CS_P(14) }
-#undef KWAGE_CS_P
-#undef KWAGE_CS_NH
+			by_planes_to_14(planes, [&](auto P) {
+				by_nh(a.num_hash, [&](auto NH) {
+					KW_GATHER_LAUNCH(ge, true, false, (count_screen_kernel<decltype(P)::value, decltype(NH)::value>), grid, block, 0, gs, a, rs.ra);
+				});
+			});
 			launch_count_refine_and_emit(planes, up, a, rs, gs, ge);
 			HIP_TRY(hipGetLastError());
 			return KWAGE_OK;
@@ -1074,7 +1045,7 @@ int launch_search_stage(Slot *sl, kwage_group *g, kwage_batch *b, const KmerLayo
 				wa.kcut = (const uint32_t*)((const uint64_t*)sl->trunc_dev.p + nq + 1);
 				a.segs = 1;
 				snprintf(sl->kernel_name, sizeof(sl->kernel_name), "count_walk_kernel<%u,%u,trunc>+refine<%d>", tplanes, std::min(a.num_hash, 5u), up);
-				launch_count_walk_planes<true>(tplanes, a, wa, rs.ra, shape, gs, ge);
+				launch_count_walk<true>(tplanes, a, wa, rs.ra, shape, gs, ge);
 				launch_count_refine_and_emit(tplanes, up, a, rs, gs, ge);
 				HIP_TRY(hipGetLastError());
 				return KWAGE_OK;
@@ -1101,7 +1072,7 @@ int launch_search_stage(Slot *sl, kwage_group *g, kwage_batch *b, const KmerLayo
 				// (shape: planes, hashes, the next step's rows prefetched, eight k-mers per step with 14 planes and more)
 				snprintf(sl->kernel_name, sizeof(sl->kernel_name), "count_walk_kernel<%u,%u,pf%s>", planes, std::min(a.num_hash, 5u), planes >= 14 ? ",8" : "");
 				wa.slot_off = nullptr; wa.kcut = nullptr;
-				launch_count_walk_planes<false>(planes, a, wa, RefineArgs(), shape, gs, ge);
+				launch_count_walk<false>(planes, a, wa, RefineArgs(), shape, gs, ge);
 				HIP_TRY(hipGetLastError());
 				return KWAGE_OK;
 			}
@@ -1127,16 +1098,8 @@ int launch_search_stage(Slot *sl, kwage_group *g, kwage_batch *b, const KmerLayo
 			// one reference file (<= 2048 columns = 16 units) or two: 4 resp. 2 queries per wave
 			const int kps = 8;
 			snprintf(sl->kernel_name, sizeof(sl->kernel_name), "count_narrow_kernel<%u,%u,%d,%d>", planes, a.num_hash, a.units_per_row <= 16 ? 4 : 2, kps);
-			if(a.units_per_row <= 16){
-				if(planes == 7){ launch_count_narrow<7, 4>(a, gs, ge); }
-				else if(planes == 10){ launch_count_narrow<10, 4>(a, gs, ge); }
-				else{ launch_count_narrow<14, 4>(a, gs, ge); }
-			}
-			else{
-				if(planes == 7){ launch_count_narrow<7, 2>(a, gs, ge); }
-				else if(planes == 10){ launch_count_narrow<10, 2>(a, gs, ge); }
-				else{ launch_count_narrow<14, 2>(a, gs, ge); }
-			}
+			if(a.units_per_row <= 16){ launch_count_narrow<4>(planes, a, gs, ge); }
+			else{ launch_count_narrow<2>(planes, a, gs, ge); }
 			HIP_TRY(hipGetLastError());
 			return KWAGE_OK;
 		}
@@ -1146,17 +1109,10 @@ int launch_search_stage(Slot *sl, kwage_group *g, kwage_batch *b, const KmerLayo
 		else{
 			snprintf(sl->kernel_name, sizeof(sl->kernel_name), "count_kernel<%u,%u>", planes, std::min(a.num_hash, 5u));
 		}
-		launch_count_planes(seg_planes, a, gs, ge);
+		launch_count(seg_planes, a, gs, ge);
 		if(a.segs > 1){
 			HIP_TRY(hipGetLastError());
-			switch(planes){
-				case 7: rc = launch_count_combine<7>(a, seg_planes, gs, ge); break;
-				case 10: rc = launch_count_combine<10>(a, seg_planes, gs, ge); break;
-				case 14: rc = launch_count_combine<14>(a, seg_planes, gs, ge); break;
-				case 20: rc = launch_count_combine<20>(a, seg_planes, gs, ge); break;
-				default: rc = launch_count_combine<32>(a, seg_planes, gs, ge); break;
-			}
-			if(rc){ return rc; }
+			if((rc = launch_count_combine(planes, a, seg_planes, gs, ge))){ return rc; }
 		}
 	}
 	HIP_TRY(hipGetLastError());

@@ -17,6 +17,7 @@
 #include <deque>
 #include <memory>
 #include <mutex>
+#include <type_traits>
 #include <vector>
 
 #include "internal.h"
@@ -476,6 +477,44 @@ int launch_remap_rows(const kwage_group *g, uint32_t n_queries, const KmerLayout
 
 // The narrowest instantiated counter width (7, 10, 14, 20 or 32 planes) whose bits hold max_count.
 uint32_t planes_for(uint64_t max_count);
+// f(integral_constant<int, PLANES>) for such a width `planes` ...
+template <typename F>
+auto by_planes(uint32_t planes, F &&f)
+{
+	switch(planes){
+		case 7: return f(std::integral_constant<int, 7>());
+		case 10: return f(std::integral_constant<int, 10>());
+		case 14: return f(std::integral_constant<int, 14>());
+		case 20: return f(std::integral_constant<int, 20>());
+		default: return f(std::integral_constant<int, 32>());
+	}
+}
+// ... f(integral_constant<int, NH>) for the instantiated hash counts: 1 to 4, and 5 for five and more ...
+template <typename F>
+auto by_nh(uint32_t nh, F &&f)
+{
+	switch(nh){
+		case 1: return f(std::integral_constant<int, 1>());
+		case 2: return f(std::integral_constant<int, 2>());
+		case 3: return f(std::integral_constant<int, 3>());
+		case 4: return f(std::integral_constant<int, 4>());
+		default: return f(std::integral_constant<int, 5>());
+	}
+}
+// ... and f(PLANES, NH) on both, as the count kernels are instantiated
+template <typename F>
+void by_shape(uint32_t planes, uint32_t nh, F &&f)
+{
+	by_planes(planes, [&](auto P) { by_nh(nh, [&](auto NH) { f(P, NH); }); });
+}
+// Before the launch of a kernel with `lds` bytes of dynamic LDS: above 48 KiB the limit has to be raised (the combine
+// kernels' tree at 32 planes, queries above 2^20 positions).  The attribute is per device, so it is set per launch.
+template <typename KERNEL>
+int allow_dynamic_lds(KERNEL kernel, size_t lds)
+{
+	if(lds > 48*1024){ HIP_TRY(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); }
+	return KWAGE_OK;
+}
 // Sets a.segs / a.seg_kmers from a.n_queries and a.chunks: how many segments each query's k-mer list is cut into, at
 // most max_segs (force_segs > 0: the tuning knob's count instead of the rule's).
 void choose_segments(SearchArgs &a, uint64_t max_kmers, uint64_t max_segs, int64_t force_segs);

@@ -423,6 +423,21 @@ __device__ __forceinline__ void tile_coords(const SearchArgs &a, uint64_t tile, 
 	c = rem % a.chunks;
 }
 
+// The lane's 16-byte unit of column tile c: u0, `live` where it lies inside the row, and `unit`, the one to load from --
+// a dead lane's is clamped to the row's last unit, so that its loads stay in bounds.
+__device__ __forceinline__ void tile_lane(const SearchArgs &a, uint32_t c, uint32_t lane, uint32_t &u0, bool &live, uint32_t &unit)
+{
+	u0 = c*WAVE + lane;
+	live = (u0 < a.units_per_row);
+	unit = live ? u0 : (a.units_per_row - 1);
+}
+
+// the real columns among the lane's 128: none in a dead lane
+__device__ __forceinline__ u32x4 valid_mask(const SearchArgs &a, uint32_t unit, bool live)
+{
+	return live ? reinterpret_cast<const u32x4*>(a.valid)[unit] : (u32x4)(0u);
+}
+
 // threshold == 1.0f: AND of every addressed row (kwage.cpp:404-470).
 //   VEC    16-byte vectors per lane per row (tile = 64*VEC*16 bytes of each row per wave)
 //   SEG    the query's row list is split over several waves (see SearchArgs::segs)
@@ -1253,6 +1268,16 @@ __device__ __forceinline__ u32x4 planes_ge(const u32x4 (&plane)[PLANES], uint32_
 	return ge;
 }
 
+// kwage.cpp:478-481 per tile: no column of the wave's tile can still reach thr even if every one of the `remaining`
+// k-mers matched (max count + remaining < threshold).  Wave-uniform.
+template <int PLANES>
+__device__ __forceinline__ bool tile_cannot_pass(const u32x4 (&plane)[PLANES], uint32_t thr, uint32_t remaining)
+{
+	if(thr <= remaining){ return false; }
+	const u32x4 can = planes_ge<PLANES>(plane, thr - remaining);
+	return !__any((can.x | can.y | can.z | can.w) != 0);
+}
+
 // columns with count >= thr (kwage.cpp:497); then the count of every surviving column is
 // re-assembled from the planes (num_match = match_count[i]).  Every lane of the wave must call it
 // (`on` = the lane holds a real tile position): the records are placed with one atomic per wave.
@@ -1417,23 +1442,15 @@ __global__ __launch_bounds__(SEARCH_THREADS) void count_kernel(SearchArgs a)
 	const uint32_t nk = k1 - k0;
 	const uint32_t *rq = a.rows + (a.pos_off[q] + k0)*NH;
 
-	const uint32_t u0 = c*WAVE + lane;
-	const bool live = (u0 < a.units_per_row);
-	const uint32_t unit = live ? u0 : (a.units_per_row - 1);
-
+	uint32_t u0, unit;
+	bool live;
+	tile_lane(a, c, lane, u0, live, unit);
 	u32x4 plane[PLANES];
 #pragma unroll
 	for(int p = 0; p < PLANES; ++p){ plane[p] = (u32x4)(0u); }
-
-	// kwage.cpp:478-481 per tile: stop once no column of the tile can still reach the threshold even if every
-	// remaining k-mer matched (max count + remaining < threshold)
 	const bool whole = count_kmers<PLANES, NH>(a.db, a.stride, rq, nk, unit, plane, [&](uint32_t done) -> bool {
 		if(SEG || !a.early_exit){ return false; }
-		const uint32_t remaining = nk - done;
-		const uint32_t thr = a.qthr[q];
-		if(thr <= remaining){ return false; }
-		const u32x4 can = planes_ge<PLANES>(plane, thr - remaining);
-		return !__any((can.x | can.y | can.z | can.w) != 0);
+		return tile_cannot_pass<PLANES>(plane, a.qthr[q], nk - done);
 	});
 	if(!whole){ return; }
 
@@ -2027,6 +2044,8 @@ __global__ __launch_bounds__(COMBINE_WAVES*WAVE) void count_combine_kernel(Searc
 	u32x4 plane[PLANES];
 #pragma unroll
 	for(int p = 0; p < PLANES; ++p){ plane[p] = (u32x4)(0u); }
+	// (combine_segments' loops, written out: through the function the compiler lays the blocks of emit_count_hits out
+	// differently -- one v_lshlrev and one v_add fewer in the text -- and this kernel's code is kept as it was measured)
 	for(uint32_t sg = w; sg < nseg; sg += COMBINE_WAVES){
 		const u32x4 *s2 = slab + (uint64_t)sg*seg_planes*a.units_per_row;
 		planes_accumulate<PLANES>(plane, (int)seg_planes, [&](int p){ return s2[(uint64_t)p*a.units_per_row]; });
@@ -2044,6 +2063,33 @@ __global__ __launch_bounds__(COMBINE_WAVES*WAVE) void count_combine_kernel(Searc
 		__syncthreads();
 	}
 	if(w == 0){ emit_count_hits<PLANES>(a, q, unit, plane, a.qthr[q], (uint64_t)q*a.runs_per_query + blockIdx.x, on); }
+}
+
+// The same sum for the combine kernels of the other counted searches (top-k, scores, presence): query q's (n > 0 k-mers)
+// segment counters of `unit` added into `plane`, the total left in wave 0's.  Every wave of the workgroup calls it; w:
+// its wave (uniform), red: the workgroup's (COMBINE_WAVES/2) x PLANES x 64 x 16 B of LDS.
+template <int PLANES>
+__device__ __forceinline__ void combine_segments(const SearchArgs &a, uint32_t q, uint32_t unit, uint32_t n, uint32_t seg_planes, uint32_t w, uint32_t lane,
+                                                 u32x4 (*red)[PLANES][WAVE], u32x4 (&plane)[PLANES])
+{
+	const uint32_t nseg = (n + a.seg_kmers - 1)/a.seg_kmers;
+	const u32x4 *slab = reinterpret_cast<const u32x4*>(a.partial) + (uint64_t)q*a.segs*seg_planes*a.units_per_row + unit;
+	for(uint32_t sg = w; sg < nseg; sg += COMBINE_WAVES){
+		const u32x4 *s2 = slab + (uint64_t)sg*seg_planes*a.units_per_row;
+		planes_accumulate<PLANES>(plane, (int)seg_planes, [&](int p){ return s2[(uint64_t)p*a.units_per_row]; });
+	}
+#pragma unroll
+	for(int half = COMBINE_WAVES/2; half >= 1; half >>= 1){
+		if(w >= (uint32_t)half && w < 2u*half){
+#pragma unroll
+			for(int p = 0; p < PLANES; ++p){ red[w - half][p][lane] = plane[p]; }
+		}
+		__syncthreads();
+		if(w < (uint32_t)half){
+			planes_accumulate<PLANES>(plane, PLANES, [&](int p){ return red[w][p][lane]; });
+		}
+		__syncthreads();
+	}
 }
 
 // (stream_read_kernel: engine.hip)

@@ -1,6 +1,7 @@
-// kwage_amd/csrc/pool_blocks.hpp -- what the synchronous calls of topk.hip, topk_merge.hip, scores.hip and filterset.hip
-// share: the device blocks of one call, taken from the context's batch pool and handed back when the call ends; the
-// tail every entry point ends through (settle); the events of a timed call; the k-mer stage into blocks of the call.
+// kwage_amd/csrc/pool_blocks.hpp -- what the synchronous calls of topk.hip, topk_merge.hip, scores.hip, presence.hip and
+// filterset.hip share: the refusals every search starts with (search_check); the device blocks of one call, taken from
+// the context's batch pool and handed back when the call ends; the tail every entry point ends through (settle); the
+// events of a timed call and the timed section; the k-mer stage into blocks of the call.
 #ifndef KWAGE_AMD_POOL_BLOCKS_HPP
 #define KWAGE_AMD_POOL_BLOCKS_HPP
 
@@ -9,6 +10,14 @@
 #include "engine_state.hpp"
 
 namespace kwage {
+
+// What every search of a batch in a group refuses first.
+inline int search_check(const kwage_group *g, const kwage_batch *b)
+{
+	if(!g->finalized){ return fail(KWAGE_ERR_STATE, "kwage_group_finalize() must be called before searching"); }
+	if(b->ctx != g->ctx){ return fail(KWAGE_ERR_ARG, "batch and group belong to different contexts"); }
+	return KWAGE_OK;
+}
 
 struct PoolBlocks {
 	DevPool *pool;
@@ -52,6 +61,21 @@ struct Events {
 	}
 };
 
+// What body() queues on s, then the wait for s.  timing: between two events, whose distance goes to *ms.
+template <typename Body>
+int timed_section(bool timing, hipStream_t s, float *ms, Body &&body)
+{
+	int rc;
+	Events<2> ev;
+	if(timing && (rc = ev.create())){ return rc; }
+	if(timing){ HIP_TRY(hipEventRecord(ev.ev[0], s)); }
+	if((rc = body())){ return rc; }
+	if(timing){ HIP_TRY(hipEventRecord(ev.ev[1], s)); }
+	HIP_TRY(hipStreamSynchronize(s));
+	if(timing){ HIP_TRY(hipEventElapsedTime(ms, ev.ev[0], ev.ev[1])); }
+	return KWAGE_OK;
+}
+
 // What the k-mer stage of a call leaves in its blocks: the row indices, and per query (batch order) the k-mer count,
 // the floor and -- where asked for -- one more word for the caller; the 8-byte aligned counter of row indices a sparse
 // group does not hold.
@@ -92,6 +116,24 @@ inline int kmer_prologue(const kwage_group *g, kwage_batch *b, const KmerLayout 
 	}
 	if(timed){ HIP_TRY(hipEventRecord(timed[1], s)); }
 	*out = k;
+	return KWAGE_OK;
+}
+
+// The k-mer stage of a search that writes into the caller's memory: kmer_prologue, then -- waited for -- the refusal of
+// a sparse group made for other queries, before anything is written; then the queued copy of the k-mer counts, final
+// here, to nkmer_dev (null: none), ahead of what the caller queues next.
+inline int kmer_prologue_checked(const kwage_group *g, kwage_batch *b, const KmerLayout *L, float threshold, void *nkmer_dev,
+                                 PoolBlocks &blocks, hipStream_t s, KmerBlocks *out)
+{
+	int rc;
+	if((rc = kmer_prologue(g, b, L, threshold, false, false, nullptr, blocks, s, out))){ return rc; }
+	if(b->n && g->d_row_map){
+		unsigned long long missing = 0;
+		HIP_TRY(hipMemcpyAsync(&missing, out->missing, sizeof(missing), hipMemcpyDeviceToHost, s));
+		HIP_TRY(hipStreamSynchronize(s));
+		if(missing){ return fail_missing_rows(missing); }
+	}
+	if(b->n && nkmer_dev){ HIP_TRY(hipMemcpyAsync(nkmer_dev, out->nkmer, (size_t)b->n*sizeof(uint32_t), hipMemcpyDefault, s)); }
 	return KWAGE_OK;
 }
 

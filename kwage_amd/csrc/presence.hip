@@ -47,8 +47,8 @@ uint64_t written_bytes(const kwage_group *g) { return (g->next_byte + 15)/16*16;
 // Everything that can be refused without the device.
 int presence_check(kwage_group *g, kwage_batch *b, float threshold, uint64_t row_bytes, const char *what)
 {
-	if(!g->finalized){ return fail(KWAGE_ERR_STATE, "kwage_group_finalize() must be called before searching"); }
-	if(b->ctx != g->ctx){ return fail(KWAGE_ERR_ARG, "batch and group belong to different contexts"); }
+	int rc;
+	if((rc = search_check(g, b))){ return rc; }
 	if(!(threshold >= 0.0f && threshold <= 1.0f)){ return fail(KWAGE_ERR_ARG, "%s: threshold must satisfy 0 <= t <= 1", what); }
 	const uint64_t w = written_bytes(g);
 	if(row_bytes < w || row_bytes % 16 != 0){
@@ -112,30 +112,19 @@ int search_presence_device(kwage_group *g, kwage_batch *b, float threshold, void
 
 	// ---- k-mer stage: distinct canonical k-mers, their row indices, the floor (unsigned)(t * n) of every query ---------
 	KmerBlocks kb;
-	if((rc = kmer_prologue(g, b, L, threshold, false, false, nullptr, blocks, s, &kb))){ return rc; }
-	if(n && g->d_row_map){
-		// a sparse group made for other queries is refused before a byte is written
-		unsigned long long missing = 0;
-		HIP_TRY(hipMemcpyAsync(&missing, kb.missing, sizeof(missing), hipMemcpyDeviceToHost, s));
-		HIP_TRY(hipStreamSynchronize(s));
-		if(missing){ return fail_missing_rows(missing); }
-	}
-	// (the k-mer counts are final here: their copy is queued ahead of the presence kernels, which the call waits for)
-	if(n && num_query_kmer_dev){
-		HIP_TRY(hipMemcpyAsync(num_query_kmer_dev, kb.nkmer, (size_t)n*sizeof(uint32_t), hipMemcpyDefault, s));
-	}
+	if((rc = kmer_prologue_checked(g, b, L, threshold, num_query_kmer_dev, blocks, s, &kb))){ return rc; }
 
 	// ---- presence: tile kernels, the AND kernel, or segments + combine, slice by slice of the queries -------------------
-	const bool timing = (flags & KWAGE_SEARCH_TIMING) != 0 && search_kernel_ms;
-	Events<2> ev;
-	if(timing && (rc = ev.create())){ return rc; }
-	if(timing){ HIP_TRY(hipEventRecord(ev.ev[0], s)); }
-	PresenceArgs pa;
-	pa.out = (uint8_t*)bits_dev;
-	pa.row_bytes = row_bytes;
-	pa.w_units = (uint32_t)(written_bytes(g)/16);
-	pa.early_exit = (flags & KWAGE_SEARCH_EARLY_EXIT) ? 1 : 0;
-	if(any){
+	return timed_section((flags & KWAGE_SEARCH_TIMING) != 0 && search_kernel_ms, s, search_kernel_ms, [&]() -> int {
+		PresenceArgs pa;
+		pa.out = (uint8_t*)bits_dev;
+		pa.row_bytes = row_bytes;
+		pa.w_units = (uint32_t)(written_bytes(g)/16);
+		pa.early_exit = (flags & KWAGE_SEARCH_EARLY_EXIT) ? 1 : 0;
+		if(!any){
+			if(n && passing_dev){ HIP_TRY(hipMemsetAsync(passing_dev, 0, (size_t)n*sizeof(uint32_t), s)); }      // (a group without columns)
+			return KWAGE_OK;
+		}
 		const RowListView v = {kb.rows, L->d_pos_off, kb.nkmer, n, L->max_pos, g->params.num_hash};
 		PresenceArgs slice_pa = pa;
 		const auto next_slice = [&](const SearchArgs &a, uint32_t) -> int {
@@ -149,12 +138,8 @@ int search_presence_device(kwage_group *g, kwage_batch *b, float threshold, void
 			hipLaunchKernelGGL(presence_popcount_kernel, dim3(n), dim3(POPCOUNT_THREADS), 0, s, pa, (uint32_t*)passing_dev);
 			HIP_TRY(hipGetLastError());
 		}
-	}
-	else if(n && passing_dev){ HIP_TRY(hipMemsetAsync(passing_dev, 0, (size_t)n*sizeof(uint32_t), s)); }      // (a group without columns)
-	if(timing){ HIP_TRY(hipEventRecord(ev.ev[1], s)); }
-	HIP_TRY(hipStreamSynchronize(s));
-	if(timing){ HIP_TRY(hipEventElapsedTime(search_kernel_ms, ev.ev[0], ev.ev[1])); }
-	return KWAGE_OK;
+		return KWAGE_OK;
+	});
 }
 
 // The host form: the bitmap in a block of the call (rows W bytes apart), then one strided copy that leaves the caller's

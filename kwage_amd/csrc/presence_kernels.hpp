@@ -1,14 +1,15 @@
 // kwage_amd/csrc/presence_kernels.hpp -- gfx950 kernels of the presence search (kwage_search_presence): one bit per
 // (query, column), set where the column's k-mer count reaches the query's floor, in the byte order of a row of the
-// matrix.  Included by presence.hip only, AFTER kernels.hpp: the counting loop, the comparator, the tile decomposition
-// and the segment sums are kernels.hpp's own (count_kmers, planes_ge, tile_coords, planes_accumulate, count_kernel's
-// SEG form).
+// matrix.  Included by presence.hip only, AFTER kernels.hpp: the tile decomposition, the counting loop, the early-exit
+// rule, the comparator and the segment sums are kernels.hpp's own (tile_coords, tile_lane, count_kmers,
+// tile_cannot_pass, planes_ge, combine_segments, count_kernel's SEG form).
 //
-//   presence_tile_kernel     count_kernel's tile loop (one wave = one query x 64 units of 16 B = 8192 columns), then
-//                            planes_ge & valid stored as ONE 16-byte store per lane: the lane's four dwords already are
-//                            the matrix's bytes for its 128 columns.  No LDS, no cross-lane traffic, no atomic.
-//   presence_combine_kernel  long queries: count_kernel<SEG> leaves partial counters per segment; this adds them up
-//                            (count_combine_kernel's tree) and wave 0 compares and stores.
+//   presence_tile_kernel     one wave = one query x 64 units of 16 B = 8192 columns: tile_lane, count_kmers with
+//                            tile_cannot_pass as its stop rule, then planes_ge & valid stored as ONE 16-byte store per
+//                            lane: the lane's four dwords already are the matrix's bytes for its 128 columns.  No LDS,
+//                            no cross-lane traffic, no atomic.
+//   presence_combine_kernel  long queries: count_kernel<SEG> leaves partial counters per segment; combine_segments adds
+//                            them up and wave 0 compares and stores.
 //   presence_and_kernel      floor == the k-mer count (t = 1): and_kernel's loop, the accumulator & valid stored.
 //   presence_popcount_kernel the set bits of every query's row (asked for only with `passing`).
 //
@@ -43,31 +44,26 @@ __global__ __launch_bounds__(SEARCH_THREADS) void presence_tile_kernel(SearchArg
 	uint32_t q, sg, c;
 	tile_coords(a, tile, q, sg, c);         // (segs == 1)
 	const uint32_t n = a.nkmer[q];
-	const uint32_t u0 = c*WAVE + lane;
-	const bool live = (u0 < a.units_per_row);
-	const uint32_t unit = live ? u0 : (a.units_per_row - 1);
+	uint32_t u0, unit;
+	bool live;
+	tile_lane(a, c, lane, u0, live, unit);
 	u32x4 bits = (u32x4)(0u);
 	if(n){                                  // (a query without k-mers: a row of zeros)
 		const uint32_t thr = a.qthr[q];
 		const uint32_t *rq = a.rows + a.pos_off[q]*NH;
 		u32x4 plane[PLANES];
-#pragma unroll
-		for(int p = 0; p < PLANES; ++p){ plane[p] = (u32x4)(0u); }
-		// count_kernel's rule: no column of the tile can reach the floor even if every remaining k-mer matched
+	#pragma unroll
+	for(int p = 0; p < PLANES; ++p){ plane[p] = (u32x4)(0u); }
 		const bool whole = count_kmers<PLANES, NH>(a.db, a.stride, rq, n, unit, plane, [&](uint32_t done) -> bool {
-			if(!pa.early_exit){ return false; }
-			const uint32_t remaining = n - done;
-			if(thr <= remaining){ return false; }
-			const u32x4 can = planes_ge<PLANES>(plane, thr - remaining);
-			return !__any((can.x | can.y | can.z | can.w) != 0);
+			return pa.early_exit && tile_cannot_pass<PLANES>(plane, thr, n - done);
 		});
 		if(whole && live){ bits = planes_ge<PLANES>(plane, thr) & reinterpret_cast<const u32x4*>(a.valid)[unit]; }
 	}
 	store_presence(pa, q, u0, bits);
 }
 
-// count_combine_kernel's sum of the segments' partial counters (slab [query][segment][seg_planes][unit]), then the
-// compare-and-store by wave 0.  One workgroup per (query, tile of 64 units).
+// combine_segments over the segments' partial counters, then the compare-and-store by wave 0.  One workgroup per
+// (query, tile of 64 units).
 template <int PLANES>
 __global__ __launch_bounds__(COMBINE_WAVES*WAVE) void presence_combine_kernel(SearchArgs a, PresenceArgs pa, uint32_t seg_planes)
 {
@@ -77,31 +73,14 @@ __global__ __launch_bounds__(COMBINE_WAVES*WAVE) void presence_combine_kernel(Se
 	const uint32_t w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
 	const uint32_t q = blockIdx.x / a.chunks, c = blockIdx.x % a.chunks;
 	const uint32_t n = a.nkmer[q];
-	const uint32_t u0 = c*WAVE + lane;
-	const bool on = (u0 < a.units_per_row);
-	const uint32_t unit = on ? u0 : (a.units_per_row - 1);
+	uint32_t u0, unit;
+	bool on;
+	tile_lane(a, c, lane, u0, on, unit);
 	u32x4 plane[PLANES];
 #pragma unroll
 	for(int p = 0; p < PLANES; ++p){ plane[p] = (u32x4)(0u); }
 	if(n){                                                 // uniform per workgroup
-		const uint32_t nseg = (n + a.seg_kmers - 1)/a.seg_kmers;
-		const u32x4 *slab = reinterpret_cast<const u32x4*>(a.partial) + (uint64_t)q*a.segs*seg_planes*a.units_per_row + unit;
-		for(uint32_t sg = w; sg < nseg; sg += COMBINE_WAVES){
-			const u32x4 *s2 = slab + (uint64_t)sg*seg_planes*a.units_per_row;
-			planes_accumulate<PLANES>(plane, (int)seg_planes, [&](int p){ return s2[(uint64_t)p*a.units_per_row]; });
-		}
-#pragma unroll
-		for(int half = COMBINE_WAVES/2; half >= 1; half >>= 1){
-			if(w >= (uint32_t)half && w < 2u*half){
-#pragma unroll
-				for(int p = 0; p < PLANES; ++p){ red[w - half][p][lane] = plane[p]; }
-			}
-			__syncthreads();
-			if(w < (uint32_t)half){
-				planes_accumulate<PLANES>(plane, PLANES, [&](int p){ return red[w][p][lane]; });
-			}
-			__syncthreads();
-		}
+		combine_segments<PLANES>(a, q, unit, n, seg_planes, w, lane, red, plane);
 	}
 	if(w == 0){
 		u32x4 bits = (u32x4)(0u);
@@ -122,9 +101,9 @@ __global__ __launch_bounds__(SEARCH_THREADS) void presence_and_kernel(SearchArgs
 	uint32_t q, sg, c;
 	tile_coords(a, tile, q, sg, c);         // (segs == 1)
 	const uint32_t n = a.nkmer[q];
-	const uint32_t u0 = c*WAVE + lane;
-	const bool live = (u0 < a.units_per_row);
-	const uint32_t unit = live ? u0 : (a.units_per_row - 1);
+	uint32_t u0, unit;
+	bool live;
+	tile_lane(a, c, lane, u0, live, unit);
 	u32x4 acc = (u32x4)(0u);
 	if(n){
 		const uint32_t nrows = n*a.num_hash;

@@ -50,8 +50,8 @@ struct ScoreKernels {
 // Everything that can be refused without the device.
 int scores_check(kwage_group *g, kwage_batch *b, uint64_t row_elems, const char *what)
 {
-	if(!g->finalized){ return fail(KWAGE_ERR_STATE, "kwage_group_finalize() must be called before searching"); }
-	if(b->ctx != g->ctx){ return fail(KWAGE_ERR_ARG, "batch and group belong to different contexts"); }
+	int rc;
+	if((rc = search_check(g, b))){ return rc; }
 	const uint64_t span = g->next_byte*8;
 	if(row_elems < span || row_elems % 4 != 0){
 		return fail(KWAGE_ERR_ARG, "%s: row_elems must be a multiple of 4 and at least the group's column span %llu (got %llu)", what,
@@ -76,27 +76,18 @@ int score_stage_plan(const kwage_group *g, uint32_t n, uint64_t max_count, TileP
 int score_stage_run(kwage_group *g, const RowListView &v, const TilePlan &plan, ScoreArgs sa, uint32_t flags, float *ms,
                     PoolBlocks &blocks, char *kernel_name)
 {
-	int rc;
 	kwage_ctx *ctx = g->ctx;
 	hipStream_t s = ctx->stream;
 	const uint64_t span = g->next_byte*8;
-	const bool timing = (flags & KWAGE_SEARCH_TIMING) != 0 && ms;
-	Events<2> ev;
-	if(timing && (rc = ev.create())){ return rc; }
-	if(timing){ HIP_TRY(hipEventRecord(ev.ev[0], s)); }
-	if(v.n && span){
+	return timed_section((flags & KWAGE_SEARCH_TIMING) != 0 && ms, s, ms, [&]() -> int {
+		if(!v.n || !span){ return KWAGE_OK; }
 		sa.span = span;
 		sa.form = (ctx->tune.scores_form == (int64_t)SCORES_FORM_LANE) ? SCORES_FORM_LANE : SCORES_FORM_WAVE;
-		rc = run_tile_slices<ScoreKernels>(g, v, nullptr, plan, sa, blocks, kernel_name, s, [&](const SearchArgs &a, uint32_t) -> int {
+		return run_tile_slices<ScoreKernels>(g, v, nullptr, plan, sa, blocks, kernel_name, s, [&](const SearchArgs &a, uint32_t) -> int {
 			sa.out += (uint64_t)a.n_queries*sa.row_elems;
 			return KWAGE_OK;
 		});
-		if(rc){ return rc; }
-	}
-	if(timing){ HIP_TRY(hipEventRecord(ev.ev[1], s)); }
-	HIP_TRY(hipStreamSynchronize(s));
-	if(timing){ HIP_TRY(hipEventElapsedTime(ms, ev.ev[0], ev.ev[1])); }
-	return KWAGE_OK;
+	});
 }
 
 namespace {
@@ -123,18 +114,7 @@ int search_scores_device(kwage_group *g, kwage_batch *b, void *scores_dev, uint6
 
 	// ---- k-mer stage: distinct canonical k-mers and their row indices (threshold 0: every floor is 0) ------------------
 	KmerBlocks kb;
-	if((rc = kmer_prologue(g, b, L, 0.0f, false, false, nullptr, blocks, s, &kb))){ return rc; }
-	if(n && g->d_row_map){
-		// a sparse group made for other queries is refused before a cell is written
-		unsigned long long missing = 0;
-		HIP_TRY(hipMemcpyAsync(&missing, kb.missing, sizeof(missing), hipMemcpyDeviceToHost, s));
-		HIP_TRY(hipStreamSynchronize(s));
-		if(missing){ return fail_missing_rows(missing); }
-	}
-	// (the k-mer counts are final here: their copy is queued ahead of the score stage, which waits for the stream)
-	if(n && num_query_kmer_dev){
-		HIP_TRY(hipMemcpyAsync(num_query_kmer_dev, kb.nkmer, (size_t)n*sizeof(uint32_t), hipMemcpyDefault, s));
-	}
+	if((rc = kmer_prologue_checked(g, b, L, 0.0f, num_query_kmer_dev, blocks, s, &kb))){ return rc; }
 
 	const RowListView v = {kb.rows, L->d_pos_off, kb.nkmer, n, L->max_pos, g->params.num_hash};
 	ScoreArgs sa;

@@ -1,12 +1,12 @@
 // kwage_amd/csrc/scores_kernels.hpp -- gfx950 kernels of the dense score search (kwage_search_scores): every query's
 // k-mer count for every column of a group, written as a queries x columns matrix of uint32 cells.  Included by
-// scores.hip only, AFTER kernels.hpp: the counting loop, the tile decomposition and the segment sums are kernels.hpp's
-// own (count_kmers, tile_coords, planes_accumulate, count_kernel's SEG form).
+// scores.hip only, AFTER kernels.hpp: the tile decomposition, the counting loop, the real-column mask and the segment
+// sums are kernels.hpp's own (tile_coords, tile_lane, count_kmers, valid_mask, combine_segments, count_kernel's SEG form).
 //
-//   score_tile_kernel     count_kernel's tile loop (one wave = one query x 64 units of 16 B = 8192 columns), then the
+//   score_tile_kernel     one wave = one query x 64 units of 16 B = 8192 columns: tile_lane, count_kmers, then the
 //                         expand-and-store epilogue in place of emit_count_hits: no atomic, no hit list.
-//   score_combine_kernel  long queries: count_kernel<SEG> leaves partial counters per segment; this adds them up
-//                         (count_combine_kernel's tree) and wave 0 runs the same epilogue.
+//   score_combine_kernel  long queries: count_kernel<SEG> leaves partial counters per segment; combine_segments adds
+//                         them up and wave 0 runs the same epilogue.
 //
 // The epilogue turns the bit-sliced counters of a tile -- PLANES x 4 dwords per lane for the lane's 128 consecutive
 // columns -- into 8192 cells (32 KiB) in 16-byte stores.  Two forms, chosen per launch (ScoreArgs::form):
@@ -108,24 +108,24 @@ __global__ __launch_bounds__(SEARCH_THREADS) void score_tile_kernel(SearchArgs a
 	uint32_t q, sg, c;
 	tile_coords(a, tile, q, sg, c);         // (segs == 1)
 	const uint32_t n = a.nkmer[q];
-	const uint32_t u0 = c*WAVE + lane;
-	const bool live = (u0 < a.units_per_row);
-	const uint32_t unit = live ? u0 : (a.units_per_row - 1);
+	uint32_t u0, unit;
+	bool live;
+	tile_lane(a, c, lane, u0, live, unit);
 	u32x4 plane[PLANES];
 #pragma unroll
 	for(int p = 0; p < PLANES; ++p){ plane[p] = (u32x4)(0u); }
 	if(n){                                  // (a query without k-mers: a row of zeros)
 		const uint32_t *rq = a.rows + a.pos_off[q]*NH;
 		(void)count_kmers<PLANES, NH>(a.db, a.stride, rq, n, unit, plane, [](uint32_t) -> bool { return false; });
-		const u32x4 ok = live ? reinterpret_cast<const u32x4*>(a.valid)[unit] : (u32x4)(0u);
+		const u32x4 ok = valid_mask(a, unit, live);
 #pragma unroll
 		for(int p = 0; p < PLANES; ++p){ plane[p] &= ok; }
 	}
 	store_scores<PLANES>(sa, plane, sa.out + (unsigned long long)q*sa.row_elems, (unsigned long long)c*(WAVE*128u), xch[threadIdx.x >> 6]);
 }
 
-// count_combine_kernel's sum of the segments' partial counters (slab [query][segment][seg_planes][unit]), then the
-// epilogue by wave 0, which takes the tree's LDS for its exchange.  One workgroup per (query, tile of 64 units).
+// combine_segments over the segments' partial counters, then the epilogue by wave 0, which takes the tree's LDS for its
+// exchange.  One workgroup per (query, tile of 64 units).
 template <int PLANES>
 __global__ __launch_bounds__(COMBINE_WAVES*WAVE) void score_combine_kernel(SearchArgs a, ScoreArgs sa, uint32_t seg_planes)
 {
@@ -135,34 +135,17 @@ __global__ __launch_bounds__(COMBINE_WAVES*WAVE) void score_combine_kernel(Searc
 	const uint32_t w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
 	const uint32_t q = blockIdx.x / a.chunks, c = blockIdx.x % a.chunks;
 	const uint32_t n = a.nkmer[q];
-	const uint32_t u0 = c*WAVE + lane;
-	const bool on = (u0 < a.units_per_row);
-	const uint32_t unit = on ? u0 : (a.units_per_row - 1);
+	uint32_t u0, unit;
+	bool on;
+	tile_lane(a, c, lane, u0, on, unit);
 	u32x4 plane[PLANES];
 #pragma unroll
 	for(int p = 0; p < PLANES; ++p){ plane[p] = (u32x4)(0u); }
 	if(n){                                                 // uniform per workgroup
-		const uint32_t nseg = (n + a.seg_kmers - 1)/a.seg_kmers;
-		const u32x4 *slab = reinterpret_cast<const u32x4*>(a.partial) + (uint64_t)q*a.segs*seg_planes*a.units_per_row + unit;
-		for(uint32_t sg = w; sg < nseg; sg += COMBINE_WAVES){
-			const u32x4 *s2 = slab + (uint64_t)sg*seg_planes*a.units_per_row;
-			planes_accumulate<PLANES>(plane, (int)seg_planes, [&](int p){ return s2[(uint64_t)p*a.units_per_row]; });
-		}
-#pragma unroll
-		for(int half = COMBINE_WAVES/2; half >= 1; half >>= 1){
-			if(w >= (uint32_t)half && w < 2u*half){
-#pragma unroll
-				for(int p = 0; p < PLANES; ++p){ red[w - half][p][lane] = plane[p]; }
-			}
-			__syncthreads();
-			if(w < (uint32_t)half){
-				planes_accumulate<PLANES>(plane, PLANES, [&](int p){ return red[w][p][lane]; });
-			}
-			__syncthreads();
-		}
+		combine_segments<PLANES>(a, q, unit, n, seg_planes, w, lane, red, plane);
 	}
 	if(w == 0){
-		const u32x4 ok = on ? reinterpret_cast<const u32x4*>(a.valid)[unit] : (u32x4)(0u);
+		const u32x4 ok = valid_mask(a, unit, on);
 #pragma unroll
 		for(int p = 0; p < PLANES; ++p){ plane[p] &= ok; }
 		store_scores<PLANES>(sa, plane, sa.out + (unsigned long long)q*sa.row_elems, (unsigned long long)c*(WAVE*128u),

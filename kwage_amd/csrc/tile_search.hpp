@@ -15,40 +15,13 @@
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
-#include <type_traits>
 
 #include "engine_state.hpp"
 #include "pool_blocks.hpp"
 
 namespace kwage {
 
-// f(integral_constant<int, PLANES>) for the instantiated counter width `planes` (engine.hip planes_for) ...
-template <typename F>
-auto by_planes(uint32_t planes, F &&f)
-{
-	switch(planes){
-		case 7: return f(std::integral_constant<int, 7>());
-		case 10: return f(std::integral_constant<int, 10>());
-		case 14: return f(std::integral_constant<int, 14>());
-		case 20: return f(std::integral_constant<int, 20>());
-		default: return f(std::integral_constant<int, 32>());
-	}
-}
-
-// ... and f(PLANES, NH) on (planes, hash functions), as engine.hip's count path dispatches
-template <typename F>
-void by_shape(uint32_t planes, uint32_t nh, F &&f)
-{
-	by_planes(planes, [&](auto P) {
-		switch(nh){
-			case 1: f(P, std::integral_constant<int, 1>()); break;
-			case 2: f(P, std::integral_constant<int, 2>()); break;
-			case 3: f(P, std::integral_constant<int, 3>()); break;
-			case 4: f(P, std::integral_constant<int, 4>()); break;
-			default: f(P, std::integral_constant<int, 5>()); break;
-		}
-	});
-}
+// (by_planes, by_shape: the dispatch on counter width and hash count, engine_state.hpp)
 
 // partial counters of every (query, segment, tile) of the launch into a.partial
 inline void launch_seg_count(const SearchArgs &a, uint32_t seg_planes, hipStream_t s)
@@ -68,9 +41,8 @@ int launch_combine(uint32_t planes, const SearchArgs &a, const typename K::Epi &
 		constexpr int PLANES = decltype(P)::value;
 		constexpr size_t lds = (size_t)(COMBINE_WAVES/2)*PLANES*WAVE*16;
 		const auto kernel = K::template combine<PLANES>();
-		if(lds > 48*1024){
-			HIP_TRY(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-		}
+		int rc;
+		if((rc = allow_dynamic_lds(kernel, lds))){ return rc; }
 		hipLaunchKernelGGL(kernel, dim3(a.n_queries*a.chunks), dim3(COMBINE_WAVES*WAVE), lds, s, a, e, seg_planes);
 		return KWAGE_OK;
 	});

@@ -103,8 +103,8 @@ int topk_select(kwage_group *g, kwage_batch *b, uint32_t k, float threshold, uin
 
 int topk_check(kwage_group *g, kwage_batch *b, uint32_t k, float threshold, const char *what)
 {
-	if(!g->finalized){ return fail(KWAGE_ERR_STATE, "kwage_group_finalize() must be called before searching"); }
-	if(b->ctx != g->ctx){ return fail(KWAGE_ERR_ARG, "batch and group belong to different contexts"); }
+	int rc;
+	if((rc = search_check(g, b))){ return rc; }
 	if(k < 1 || k > KWAGE_TOPK_MAX){ return fail(KWAGE_ERR_ARG, "%s: k must satisfy 1 <= k <= %u (got %u)", what, (unsigned)KWAGE_TOPK_MAX, k); }
 	if(!(threshold >= 0.0f && threshold <= 1.0f)){ return fail(KWAGE_ERR_ARG, "%s: threshold must satisfy 0 <= t <= 1", what); }
 	return KWAGE_OK;

@@ -1,13 +1,13 @@
 // kwage_amd/csrc/topk_kernels.hpp -- gfx950 kernels of the top-k search (kwage_search_topk): for every query the k
-// columns with the highest counts, selected on the device.  Included by topk.hip only, AFTER kernels.hpp: the counting
-// loop, the tile decomposition and the bit-sliced comparator are kernels.hpp's own (count_kmers, planes_ge,
-// planes_accumulate, count_kernel's SEG form).
+// columns with the highest counts, selected on the device.  Included by topk.hip only, AFTER kernels.hpp: the tile
+// decomposition, the counting loop, the real-column mask, the bit-sliced comparator and the segment sums are
+// kernels.hpp's own (tile_coords, tile_lane, count_kmers, valid_mask, planes_ge, combine_segments, count_kernel's SEG form).
 //
-//   topk_tile_kernel     count_kernel's tile loop (one wave = one query x 64 units of 16 B = 8192 columns), then a
+//   topk_tile_kernel     one wave = one query x 64 units of 16 B = 8192 columns: tile_lane, count_kmers, then a
 //                        per-tile selection in place of emit_count_hits: the tile's best <= k columns go to the
 //                        tile's own slot range of the candidate buffer (no atomic anywhere).
-//   topk_combine_kernel  long queries: count_kernel<SEG> leaves partial counters per segment; this adds them up
-//                        (count_combine_kernel's tree) and selects the same way.
+//   topk_combine_kernel  long queries: count_kernel<SEG> leaves partial counters per segment; combine_segments adds
+//                        them up and wave 0 selects the same way.
 //   topk_merge_kernel    one workgroup per query: radix select over the tiles' candidates, the <= k winners written
 //                        ordered by column.
 //   topk_append_kernel   kwage_search_topk_device_append: the selected records appended to the caller's device list.
@@ -113,19 +113,18 @@ __global__ __launch_bounds__(SEARCH_THREADS) void topk_tile_kernel(SearchArgs a,
 		return;
 	}
 	const uint32_t *rq = a.rows + a.pos_off[q]*NH;
-	const uint32_t u0 = c*WAVE + lane;
-	const bool live = (u0 < a.units_per_row);
-	const uint32_t unit = live ? u0 : (a.units_per_row - 1);
+	uint32_t u0, unit;
+	bool live;
+	tile_lane(a, c, lane, u0, live, unit);
 	u32x4 plane[PLANES];
 #pragma unroll
 	for(int p = 0; p < PLANES; ++p){ plane[p] = (u32x4)(0u); }
 	(void)count_kmers<PLANES, NH>(a.db, a.stride, rq, n, unit, plane, [](uint32_t) -> bool { return false; });
-	const u32x4 ok = live ? reinterpret_cast<const u32x4*>(a.valid)[unit] : (u32x4)(0u);
+	const u32x4 ok = valid_mask(a, unit, live);
 	topk_select_tile<PLANES>(plane, ok, a.qthr[q], n, t.k, unit, t.cand + slot*t.k, t.cand_n + slot);
 }
 
-// count_combine_kernel's sum of the segments' partial counters (slab [query][segment][seg_planes][unit]), then the
-// tile selection by wave 0.  One workgroup per (query, tile of 64 units).
+// combine_segments over the segments' partial counters, then the tile selection by wave 0.  One workgroup per (query, tile of 64 units).
 template <int PLANES>
 __global__ __launch_bounds__(COMBINE_WAVES*WAVE) void topk_combine_kernel(SearchArgs a, TopkArgs t, uint32_t seg_planes)
 {
@@ -140,32 +139,15 @@ __global__ __launch_bounds__(COMBINE_WAVES*WAVE) void topk_combine_kernel(Search
 		if(threadIdx.x == 0){ t.cand_n[slot] = 0; }
 		return;
 	}
-	const uint32_t u0 = c*WAVE + lane;
-	const bool on = (u0 < a.units_per_row);
-	const uint32_t unit = on ? u0 : (a.units_per_row - 1);
-	const uint32_t nseg = (n + a.seg_kmers - 1)/a.seg_kmers;
-	const u32x4 *slab = reinterpret_cast<const u32x4*>(a.partial) + (uint64_t)q*a.segs*seg_planes*a.units_per_row + unit;
+	uint32_t u0, unit;
+	bool on;
+	tile_lane(a, c, lane, u0, on, unit);
 	u32x4 plane[PLANES];
 #pragma unroll
 	for(int p = 0; p < PLANES; ++p){ plane[p] = (u32x4)(0u); }
-	for(uint32_t sg = w; sg < nseg; sg += COMBINE_WAVES){
-		const u32x4 *s2 = slab + (uint64_t)sg*seg_planes*a.units_per_row;
-		planes_accumulate<PLANES>(plane, (int)seg_planes, [&](int p){ return s2[(uint64_t)p*a.units_per_row]; });
-	}
-#pragma unroll
-	for(int half = COMBINE_WAVES/2; half >= 1; half >>= 1){
-		if(w >= (uint32_t)half && w < 2u*half){
-#pragma unroll
-			for(int p = 0; p < PLANES; ++p){ red[w - half][p][lane] = plane[p]; }
-		}
-		__syncthreads();
-		if(w < (uint32_t)half){
-			planes_accumulate<PLANES>(plane, PLANES, [&](int p){ return red[w][p][lane]; });
-		}
-		__syncthreads();
-	}
+	combine_segments<PLANES>(a, q, unit, n, seg_planes, w, lane, red, plane);
 	if(w == 0){
-		const u32x4 ok = on ? reinterpret_cast<const u32x4*>(a.valid)[unit] : (u32x4)(0u);
+		const u32x4 ok = valid_mask(a, unit, on);
 		topk_select_tile<PLANES>(plane, ok, a.qthr[q], n, t.k, unit, t.cand + slot*t.k, t.cand_n + slot);
 	}
 }
