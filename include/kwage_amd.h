@@ -184,6 +184,51 @@ int kwage_group_params(const kwage_group *g, kwage_params *out);
  * Any pointer may be NULL. */
 int kwage_group_placement(const kwage_group *g, uint32_t *candidates, double *kept_gbps, double *other_gbps, double *windowed_gbps);
 
+/* Live insert, no counterpart in the reference: n whole Bloom filters (filter-major, 2^L bits each, LSB first -- the
+ * payload of a `.bloom` file, what kwage_bloom_bits_from_batch writes, the layout kwage_filterset_from_bits reads;
+ * for L < 3 a filter is the low 2^L bits of its first byte) become n new columns of the group, transposed on the
+ * device.  Allowed before AND after kwage_group_finalize; a finalized group stays finalized and every search
+ * submitted after the call returns sees the new columns.  Columns already in the group keep their numbers and bits.
+ *   - filter i of the call becomes global column *first_column + i: the columns of one call are contiguous;
+ *   - inserts pack densely at BIT granularity.  If the group's last reservation was an insert, the call continues at the
+ *     very next column; otherwise (the first insert, or a file, host or random block was added since) it starts at the
+ *     next 16-byte boundary of the row, like every other block.  So 1000 filters inserted one at a time take the same
+ *     125 bytes of a row as one call of 1000, and the matrix is bit for bit what kwage_group_add_columns makes of the
+ *     transposed image.  Every other add closes the open tail (and stays refused after finalize);
+ *   - kwage_group_column_span stays a multiple of 8: 8 * ceil(tail / 8), row_bytes = ceil(tail / 8);
+ *   - in every row the call owns everything from *first_column to the end of the last 32-bit word it touches (nothing
+ *     valid lies above a group's tail): bits of the first word below *first_column % 32 are kept from memory, bits at and
+ *     above the new tail are written as zero.  One thread owns a (row, word): no atomics, no read-modify-write outside
+ *     that first word;
+ *   - afterwards the valid mask, the span and the column count include the new columns, and the bit densities a
+ *     finalized group plans its early exit with are re-sampled (planning inputs: they change no result);
+ *   - flags: KWAGE_SEARCH_TIMING fills *insert_kernel_ms (may be NULL) with the HIP-event duration of the insert
+ *     kernels; other bits are ignored.
+ * The host form reads filter i at bits + i*filter_stride_bytes (the stride is ignored when n < 2) and stages chunks of
+ * rows through the context's load buffers; the device form reads device memory in place; the third form takes n `.bloom`
+ * files, columns in the order given, validated as kwage_build_db validates its inputs -- all n before anything is written.
+ * Errors, all found before anything is written -- the span, column count, valid mask and matrix are then as before:
+ * KWAGE_ERR_ARG for a NULL argument, n == 0, a sparse group, a host filter_stride_bytes smaller than a filter with
+ * n > 1, a device pointer or stride that is not a multiple of 4, or more columns than the group's capacity holds
+ * (*first_column + n > 8 * row_stride); KWAGE_ERR_STATE while a search is pending on the context (between
+ * kwage_search_submit and its collect); for `.bloom` files KWAGE_ERR_IO (unreadable), KWAGE_ERR_FORMAT (truncated,
+ * incomplete, wrong CRC32) or KWAGE_ERR_ARG (kmer_len, num_hash, log_2_filter_len or hash_func differ from the group's).
+ * Synchronous; runs on the context's first stream. */
+int kwage_group_insert_filters(kwage_group *g, const void *bits, uint64_t filter_stride_bytes, uint32_t n,
+                               uint32_t flags, uint64_t *first_column, float *insert_kernel_ms);
+int kwage_group_insert_filters_device(kwage_group *g, const void *bits_dev, uint64_t filter_stride_bytes, uint32_t n,
+                                      uint32_t flags, uint64_t *first_column, float *insert_kernel_ms);
+int kwage_group_insert_bloom_files(kwage_group *g, const char *const *paths, uint32_t n, uint32_t flags,
+                                   uint64_t *first_column, float *insert_kernel_ms);
+/* Withdraw columns: from the call's return on they are pad columns in every sense -- never reported by any search form,
+ * 0 in score, presence and kwage_group_column_bits output, refused by kwage_filterset_from_columns, zeros in
+ * kwage_group_read_rows.  Their bits are cleared in every row (the host folds the list into distinct (32-bit word, mask)
+ * pairs, one thread per (row, pair)), their valid bits are cleared and the column count drops.  Columns may repeat within
+ * a call; groups of either kind, finalized or not.  The space is NOT reused: the span and the numbers of all other
+ * columns stay, and a later insert continues at the tail.  KWAGE_ERR_ARG, nothing changed, for a column at or beyond
+ * the span or one that is (already) a pad column; KWAGE_ERR_STATE while a search is pending.  Synchronous. */
+int kwage_group_retire_columns(kwage_group *g, const uint64_t *columns, uint64_t n);
+
 /* ------------------------------------------------------------------------------------
  * Query batch: raw sequences (any case, any characters -- exactly what the reference hands to
  * search(), kwage.cpp:119,137), concatenated, uploaded once and kept resident in HBM.

@@ -2,11 +2,9 @@
 // the bit transpose at the heart of the reference's build_db() (build_db.cpp:24-456, loop
 // :259-315: for every set bit k of filter j, set bit j of slice k -- one get_bit/set_bit pair per
 // bit, single threaded) done as a transpose of 32 x 32 bit blocks in registers on the GPU, writing a `.db` file that is
-// byte-identical to the reference's for the same `.bloom` inputs.
-//
-// `.bloom` file = binary_write<BloomFilter> (binary_io.cpp:182-208): 1 magic byte (0xFF complete),
-// BloomParam {u32 kmer_len, u32 log_2_filter_len, u32 num_hash, i32 hash_func} (bloom.h:546-556),
-// u32 crc32 of the bit array, FilterInfo (binary_io.cpp:154-163), then 2^L/8 bytes of bits.
+// byte-identical to the reference's for the same `.bloom` inputs.  The tile and its register transpose are
+// transpose_tile.hpp's (the live insert writes the same tile into a resident matrix: insert_kernels.hpp); the `.bloom`
+// files are opened and validated by bloom_files.hpp.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -17,94 +15,19 @@
 #include <thread>
 #include <vector>
 
-#include <fcntl.h>
-#include <sys/mman.h>
-#include <sys/stat.h>
-#include <unistd.h>
 #include <zlib.h>
 
+#include "bloom_files.hpp"
 #include "host.hpp"
 #include "internal.h"
+#include "transpose_tile.hpp"
 
 using namespace kwage;
 
 namespace {
 
-// One workgroup = 8 waves = a tile of FILTERS filters x ROWS slices (TransposeTile: 64 KB in, 64 KB out).
+// (TransposeTile, transpose_32x32, tile_request and tile_zero_past_end: transpose_tile.hpp)
 //
-// A lane holds a 32 x 32 bit block: one dword (32 consecutive slices) of each of 32 consecutive filters, loaded so
-// that LD consecutive lanes read consecutive dwords of the same filter (64- or 128-byte runs per filter), transposes
-// it in registers (five rounds of masked half-block swaps, ~480 integer operations for 1024 bits -- the ballot form
-// this replaces spent five instructions per 64 bits and was VALU-bound at 0.15 of the HBM rate) and leaves 32 dwords
-// in LDS: slice (32d + b), the four bytes of its 32 filters.  The tile is then written out as whole row segments of
-// FILTERS/8 bytes, 16 bytes per thread.  LDS columns are rotated by 16 bytes per 32 slices so that the lanes of
-// one store spread over the banks (rows are FILTERS/8 = 128 or 64 bytes apart).
-template<int LD, int TB_WAVES> struct TransposeTile {
-	static constexpr int WAVES = TB_WAVES;
-	static constexpr int ROWS = 32*LD;                        // slices per tile
-	static constexpr int GROUPS = TB_WAVES*(64/LD);           // 32-filter groups per tile
-	static constexpr int FILTERS = 32*GROUPS;
-	static constexpr int PITCH = GROUPS;                      // dwords per LDS row
-	static_assert(ROWS*PITCH*4 == TB_WAVES*8*1024, "8 KB per wave");
-};
-
-__device__ inline void transpose_32x32(uint32_t (&a)[32])
-{
-	// a[i] bit b  <->  a[b] bit i (both LSB-first)
-#pragma unroll
-	for(int s = 0; s < 5; ++s){
-		const int j = 16 >> s;
-		const uint32_t m = s == 0 ? 0x0000FFFFu : s == 1 ? 0x00FF00FFu : s == 2 ? 0x0F0F0F0Fu : s == 3 ? 0x33333333u : 0x55555555u;
-#pragma unroll
-		for(int k = 0; k < 32; ++k){
-			if(k & j){ continue; }
-			const uint32_t t = ((a[k] >> j) ^ a[k + j]) & m;
-			a[k + j] ^= t;
-			a[k] ^= t << j;
-		}
-	}
-}
-
-// A lane's 32 dwords of tile (row0, f0): the loads are ISSUED here and nothing else touches the values on the fast path
-// (filters past the last one read the last one's dword; tile_zero_past_end() clears them before the transpose), so the
-// caller can leave them in flight behind other work.
-template<int LD>
-__device__ __forceinline__ void tile_request(uint32_t (&a)[32], const uint8_t *__restrict__ in, uint64_t in_stride, uint32_t n_filters,
-                                             uint64_t chunk_rows, uint64_t row0, uint32_t first, uint32_t d)
-{
-	const uint64_t tile_bytes = (chunk_rows - row0 + 7)/8;    // bytes of a filter left in the chunk from the tile's first slice on
-	if(tile_bytes >= 4ull*LD && (in_stride & 3) == 0 && (((uintptr_t)in) & 3) == 0){
-		// the whole row range of the tile exists and dwords are aligned (uniform over the workgroup): 32 loads in flight
-		// per lane, no branch between them
-		const uint32_t last = first < n_filters ? std::min<uint32_t>(31u, n_filters - 1 - first) : 0u;
-		const uint8_t *base = in + (uint64_t)(first < n_filters ? first : 0u)*in_stride + row0/8 + 4*d;
-#pragma unroll
-		for(int i = 0; i < 32; ++i){
-			a[i] = *reinterpret_cast<const uint32_t*>(base + (uint64_t)std::min<uint32_t>((uint32_t)i, last)*in_stride);
-		}
-	}
-	else{
-		// the last rows of a chunk, or filters shorter than a dword: byte by byte
-		const uint32_t have = tile_bytes > 4ull*d ? (uint32_t)std::min<uint64_t>(4, tile_bytes - 4ull*d) : 0;
-#pragma unroll 1
-		for(int i = 0; i < 32; ++i){
-			const uint32_t f = first + i;
-			uint32_t v = 0;
-			if(f < n_filters){
-				const uint8_t *src = in + (uint64_t)f*in_stride + row0/8 + 4*d;
-				for(uint32_t b = 0; b < have; ++b){ v |= (uint32_t)src[b] << (8*b); }
-			}
-			a[i] = v;
-		}
-	}
-}
-
-__device__ __forceinline__ void tile_zero_past_end(uint32_t (&a)[32], uint32_t first, uint32_t n_filters)
-{
-#pragma unroll
-	for(int i = 0; i < 32; ++i){ a[i] = first + i < n_filters ? a[i] : 0u; }
-}
-
 // A workgroup takes tiles t = blockIdx.x, + gridDim.x, ... (slice tiles fastest).  The launch has one workgroup per tile.
 // (KWAGE_BUILD_PERSISTENT=1: a resident grid instead -- the next tile's 32 loads per lane are then requested before the
 // current tile is written out of LDS, so that reads and writes of a CU overlap although the 64 KB tile leaves room for
@@ -197,36 +120,6 @@ __global__ void pack_columns_kernel(uint32_t *dst, uint64_t dst_stride_words, ui
 	}
 }
 
-struct BloomFile {
-	int fd = -1;
-	const unsigned char *map = nullptr;
-	size_t size = 0;
-	uint32_t crc = 0;
-	FilterInfo info;
-	size_t bits_off = 0;
-	void close_file()
-	{
-		if(map){ munmap((void*)map, size); map = nullptr; }
-		if(fd >= 0){ close(fd); fd = -1; }
-	}
-};
-
-// f(0) ... f(nparts - 1), on threads of their own where they can be had.  A thread that cannot be created
-// (std::system_error -- which must never cross the C ABI this file exports) leaves its part to the caller.
-template <typename F>
-void run_parts(unsigned nparts, F f)
-{
-	std::vector<std::thread> pool;
-	std::vector<unsigned> mine;
-	for(unsigned t = 1; t < nparts; ++t){
-		try{ pool.emplace_back(f, t); }
-		catch(...){ mine.push_back(t); }
-	}
-	if(nparts){ f(0u); }
-	for(unsigned t : mine){ f(t); }
-	for(auto &th : pool){ th.join(); }
-}
-
 // crc32 of a large buffer continued from `crc`: parts in parallel, stitched with crc32_combine
 // (the result is identical to one sequential crc32_z call).
 uint32_t crc32_parallel(uint32_t crc, const unsigned char *buf, uint64_t len)
@@ -242,8 +135,6 @@ uint32_t crc32_parallel(uint32_t crc, const unsigned char *buf, uint64_t len)
 	for(unsigned t = 0; t < nthread && pl[t]; ++t){ out = crc32_combine(out, pc[t], (z_off_t)pl[t]); }
 	return (uint32_t)out;
 }
-
-inline uint32_t rd32(const unsigned char *p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
 
 }  // namespace
 
@@ -261,53 +152,13 @@ extern "C" int kwage_build_db(kwage_ctx *ctx, const char *out_path, const kwage_
 	hipStream_t stream = ctx_stream(ctx);
 
 	const uint64_t filter_len = 1ull << params->log_2_filter_len;
-	const uint64_t filter_bytes = (filter_len + 7)/8;
 	const uint64_t slice_size = ((uint64_t)n + 7)/8;
 
-	std::vector<BloomFile> files(n);
+	std::vector<BloomFile> files;
 	auto cleanup = [&]() { for(auto &f : files){ f.close_file(); } };
+	// open + validate every .bloom file, per-filter CRC32 included: BEFORE anything is written (bloom_files.hpp)
+	if((rc = open_bloom_files("build_db", bloom_paths, n, params, files))){ return rc; }
 
-	// ---- open + validate every .bloom file (build_db.cpp:48-181) ------------------------------
-	for(uint32_t i = 0; i < n; ++i){
-		BloomFile &f = files[i];
-		f.fd = open(bloom_paths[i], O_RDONLY);
-		struct stat st;
-		if(f.fd < 0 || fstat(f.fd, &st) != 0){ cleanup(); return fail(KWAGE_ERR_IO, "build_db: Unable to open Bloom filter file %s", bloom_paths[i]); }
-		f.size = (size_t)st.st_size;
-		if(f.size < 21){ cleanup(); return fail(KWAGE_ERR_FORMAT, "build_db: %s is truncated", bloom_paths[i]); }
-		f.map = (const unsigned char*)mmap(nullptr, f.size, PROT_READ, MAP_PRIVATE, f.fd, 0);
-		if(f.map == MAP_FAILED){ f.map = nullptr; cleanup(); return fail(KWAGE_ERR_IO, "build_db: mmap(%s) failed", bloom_paths[i]); }
-		if(f.map[0] != 0xFF){ cleanup(); return fail(KWAGE_ERR_FORMAT, "build_db: Incomplete Bloom filter %s", bloom_paths[i]); }
-		const uint32_t k = rd32(f.map + 1), lg = rd32(f.map + 5), nh = rd32(f.map + 9);
-		const int32_t hf = (int32_t)rd32(f.map + 13);
-		if(k != params->kmer_len || lg != params->log_2_filter_len || nh != params->num_hash || hf != params->hash_func){
-			cleanup();
-			return fail(KWAGE_ERR_ARG, "build_db: Inconsistent Bloom parameters in %s", bloom_paths[i]);
-		}
-		f.crc = rd32(f.map + 17);
-		size_t used = 0;
-		if(!parse_filter_info(f.map + 21, f.size - 21, f.info, &used)){ cleanup(); return fail(KWAGE_ERR_FORMAT, "build_db: Error reading Bloom filter info from %s", bloom_paths[i]); }
-		f.bits_off = 21 + used;
-		if(f.size - f.bits_off < filter_bytes){ cleanup(); return fail(KWAGE_ERR_FORMAT, "build_db: Error reading filter bytes from %s", bloom_paths[i]); }
-	}
-
-	// ---- per-filter CRC32 (build_db.cpp:343-362), host threads; checked BEFORE anything is written
-	{
-		const unsigned nthread = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
-		std::atomic<uint32_t> next(0), bad(0xFFFFFFFFu);
-		run_parts(nthread, [&](unsigned) {
-			for(uint32_t i = next++; i < n; i = next++){
-				uint64_t crc = crc32_z(0L, Z_NULL, 0);
-				crc = crc32_z(crc, files[i].map + files[i].bits_off, filter_bytes);
-				if((uint32_t)crc != files[i].crc){ bad = i; }
-			}
-		});
-		if(bad != 0xFFFFFFFFu){
-			const uint32_t i = bad;
-			cleanup();
-			return fail(KWAGE_ERR_FORMAT, "build_db: One or more invalid Bloom filter CRC32 values (%s)", bloom_paths[i]);
-		}
-	}
 
 	FILE *fout = fopen(out_path, "wb");
 	if(!fout){ cleanup(); return fail(KWAGE_ERR_IO, "build_db: Unable to open output file for writing"); }

@@ -371,6 +371,8 @@ struct kwage_group {
 	uint64_t nrows = 0;
 	uint64_t stride = 0;           // bytes, multiple of 128
 	uint64_t next_byte = 0;        // next free byte column within a row
+	uint64_t tail_column = 0;      // live insert (insert.hip): the next free COLUMN while the tail is open; next_byte == ceil(tail_column/8)
+	bool tail_open = false;        // the group's last reservation was an insert: the next insert continues at tail_column (any other block closes it)
 	uint64_t num_columns = 0;      // valid columns
 	uint8_t *d_bits = nullptr;
 	uint8_t *d_valid = nullptr;

@@ -409,7 +409,8 @@ extern "C" void kwage_group_destroy(kwage_group *g)
 
 namespace {
 
-// Reserve a 16-byte aligned byte range for `num_filter` new columns; mark them valid.
+// Reserve a 16-byte aligned byte range for `num_filter` new columns; mark them valid.  (It closes the open tail a live
+// insert left: the next insert starts on a 16-byte boundary behind this block.)
 int group_reserve_columns(kwage_group *g, uint64_t num_filter, uint64_t *byte0)
 {
 	if(g->finalized){ return fail(KWAGE_ERR_STATE, "group is finalized; no more columns can be added"); }
@@ -423,6 +424,7 @@ int group_reserve_columns(kwage_group *g, uint64_t num_filter, uint64_t *byte0)
 	for(uint64_t c = 0; c < num_filter; ++c){ g->h_valid[start + c/8] |= (uint8_t)(1u << (c%8)); }
 	g->next_byte = start + width;
 	g->num_columns += num_filter;
+	g->tail_open = false;
 	*byte0 = start;
 	return KWAGE_OK;
 }
@@ -1045,13 +1047,14 @@ extern "C" int kwage_group_read_rows(kwage_group *g, const uint32_t *rows, uint6
 	return KWAGE_OK;
 }
 
-extern "C" int kwage_group_finalize(kwage_group *g)
+namespace kwage {
+
+// The matrix's bit density, from a few thousand rows (microseconds), on the context's first stream behind an up-to-date
+// d_valid: kwage_group_finalize's probe, and what a live insert or retire re-samples (insert.hip).  The two values are
+// planning inputs and change no result; a probe that cannot run leaves the defaults.
+void group_probe_density(kwage_group *g)
 {
-	if(!g){ return fail(KWAGE_ERR_ARG, "kwage_group_finalize: NULL group"); }
 	kwage_ctx *ctx = g->ctx;
-	int rc = set_device(ctx);
-	if(rc){ return rc; }
-	HIP_TRY(hipMemcpyAsync(g->d_valid, g->h_valid.data(), g->stride, hipMemcpyHostToDevice, ctx->stream));
 	// the matrix's bit density, from a few thousand rows (microseconds): what the early exit over long queries at t < 1 plans with
 	// (and its densest column's: what the bound has to rule out before a 128-byte group can be dropped)
 	g->density = 0.25;
@@ -1076,6 +1079,18 @@ extern "C" int kwage_group_finalize(kwage_group *g)
 			(void)hipFree(d_probe);
 		}
 	}
+}
+
+}  // namespace kwage
+
+extern "C" int kwage_group_finalize(kwage_group *g)
+{
+	if(!g){ return fail(KWAGE_ERR_ARG, "kwage_group_finalize: NULL group"); }
+	kwage_ctx *ctx = g->ctx;
+	int rc = set_device(ctx);
+	if(rc){ return rc; }
+	HIP_TRY(hipMemcpyAsync(g->d_valid, g->h_valid.data(), g->stride, hipMemcpyHostToDevice, ctx->stream));
+	group_probe_density(g);
 	HIP_TRY(hipStreamSynchronize(ctx->stream));
 	release_mapping(ctx);          // the last file's copies are done
 	g->finalized = true;

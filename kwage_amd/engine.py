@@ -168,6 +168,58 @@ class Group:
         self._real.append((first.value, num_columns))
         return first.value
 
+    def _inserted(self, first: int, n: int) -> int:
+        self._real.append((first, n))
+        self._column_bits = None                     # (a live group changes: column_bits() is computed afresh)
+        return first
+
+    def insert_filters(self, bits, flags: int = 0) -> int:
+        """Live insert (kwage_group_insert_filters): n whole Bloom filters become n new columns, before or after
+        finalize(); returns the first one's column.  bits: uint8 [n, max(1, 2^L / 8)], LSB first -- `.bloom` payloads,
+        kwage_bloom_bits_from_batch's output.  A numpy array takes the host form (rows may lie further apart than a
+        filter), a CUDA tensor the device form."""
+        first = C.c_uint64()
+        if isinstance(bits, np.ndarray):
+            assert bits.dtype == np.uint8 and bits.ndim == 2 and bits.shape[1] >= max(1, self._nrows // 8), bits.shape
+            assert bits.shape[0] <= 1 or bits.strides[1] == 1 and bits.strides[0] >= bits.shape[1], bits.strides
+            if bits.shape[0] and bits.strides[1] != 1:
+                bits = np.ascontiguousarray(bits)
+            check(lib().kwage_group_insert_filters(self._h, bits.ctypes.data if bits.size else None, bits.strides[0], bits.shape[0],
+                                                   flags, C.byref(first), None))
+        else:
+            import torch
+            assert bits.is_cuda and bits.dtype == torch.uint8 and bits.dim() == 2 and (bits.shape[0] <= 1 or bits.stride(1) == 1), "insert_filters: a uint8 [n, bytes] CUDA tensor"
+            assert bits.shape[1] >= max(1, self._nrows // 8), bits.shape
+            check(lib().kwage_group_insert_filters_device(self._h, bits.data_ptr() if bits.numel() else None, bits.stride(0), bits.shape[0],
+                                                          flags, C.byref(first), None))
+        return self._inserted(first.value, bits.shape[0])
+
+    def insert_bloom_files(self, paths: Sequence[str], flags: int = 0) -> int:
+        """The live insert from `.bloom` files (kwage_group_insert_bloom_files), columns in the order given; returns the
+        first one's column."""
+        n = len(paths)
+        arr = (C.c_char_p * n)(*[p.encode() for p in paths])
+        first = C.c_uint64()
+        check(lib().kwage_group_insert_bloom_files(self._h, arr, n, flags, C.byref(first), None))
+        return self._inserted(first.value, n)
+
+    def retire_columns(self, cols: Sequence[int]) -> None:
+        """Withdraw columns (kwage_group_retire_columns): pad columns from here on; their space is not reused."""
+        cols = np.ascontiguousarray(cols, dtype=np.uint64)
+        check(lib().kwage_group_retire_columns(self._h, cols.ctypes.data if cols.size else None, cols.size))
+        gone = sorted(set(int(c) for c in cols.tolist()))
+        real = []
+        for first, nf in self._real:                 # cut the retired columns out of the blocks that held them
+            at = first
+            for c in [c for c in gone if first <= c < first + nf]:
+                if c > at:
+                    real.append((at, c - at))
+                at = c + 1
+            if first + nf > at:
+                real.append((at, first + nf - at))
+        self._real = real
+        self._column_bits = None
+
     def set_bits(self, rows: np.ndarray, columns: np.ndarray) -> None:
         rows = np.ascontiguousarray(rows, dtype=np.uint32)
         columns = np.ascontiguousarray(columns, dtype=np.uint64)
@@ -192,7 +244,7 @@ class Group:
 
     def column_bits(self) -> np.ndarray:
         """kwage_group_column_bits(): the set-bit count of every column (uint32 [column_span], 0 on pad columns) -- the
-        denominator of a Jaccard index.  Computed once per group and kept (a group is finalized: it no longer changes)."""
+        denominator of a Jaccard index.  Computed once per group and kept until a live insert or retire changes the group."""
         if self._column_bits is None:
             out = np.zeros(self.column_span, dtype=np.uint32)
             check(lib().kwage_group_column_bits(self._h, out.ctypes.data if out.size else None))
@@ -740,12 +792,23 @@ class DatabaseHit:
     num_query_kmer: int
 
 
+class _LiveBlock(str):
+    """The `path` of a block of live-inserted samples in FileDatabase._layout: the string "live", carrying the run
+    accessions recorded for the block's columns (no file holds them)."""
+    def __new__(cls, accessions):
+        self = super().__new__(cls, "live")
+        self.accessions = list(accessions)
+        return self
+
+
 class FileDatabase(Database):
     """A directory tree / list of `.db` (`.dbz`) files loaded the way the `kwage` CLI loads it: files
     grouped by (kmer_len, num_hash, log_2_filter_len, hash_func), each group one HBM matrix; hits are
-    mapped back to (file, column) and carry the sample's run accession."""
+    mapped back to (file, column) and carry the sample's run accession.  With headroom > 0 every group has room for
+    that many more columns: add_sample() makes new samples searchable in the resident groups (live insert),
+    retire_sample() withdraws one."""
 
-    def __init__(self, ctx: Context, paths: Sequence[str]):
+    def __init__(self, ctx: Context, paths: Sequence[str], headroom: int = 0):
         import os
         files: List[str] = []
         todo = list(paths)
@@ -772,7 +835,8 @@ class FileDatabase(Database):
             span = 0
             for _, nf in members:
                 span = (span + 15) // 16 * 16 + (nf + 7) // 8
-            g = Group(ctx, k, nh, lg, span * 8, hf)
+            # (live inserts start on the 16-byte boundary behind the files)
+            g = Group(ctx, k, nh, lg, span * 8 if headroom <= 0 else (span + 15) // 16 * 16 * 8 + headroom, hf)
             firsts = [(first, nf, f) for (first, nf), (f, _) in zip(g.add_db_files([f for f, _ in members]), members)]
             g.finalize()
             groups.append(g)
@@ -780,8 +844,55 @@ class FileDatabase(Database):
         super().__init__(groups)
         self.ctx = ctx
         self.files = files
+        self._retired = set()                         # (group index, column) of the FILE columns retire_sample() withdrew
+
+    def _blocks(self):
+        """(group index, first column, columns, path) of every block in report order: the files in file order, then the
+        live blocks group by group."""
+        where = {path: (gi, first, nf) for gi, layout in enumerate(self._layout) for first, nf, path in layout if not isinstance(path, _LiveBlock)}
+        out = [where[f] + (f,) for f in self.files]
+        out.extend((gi, first, nf, path) for gi, layout in enumerate(self._layout) for first, nf, path in layout if isinstance(path, _LiveBlock))
+        return out
+
+    def _samples(self):
+        """(group index, column in the group, path, column in the block) of every sample in report order."""
+        return [(gi, first + c, path, c) for gi, first, nf, path in self._blocks() for c in range(nf) if (gi, first + c) not in self._retired]
+
+    def add_sample(self, accession: str, seqs: Sequence[bytes | str], group: int = 0) -> Tuple[int, int]:
+        """Make one new sample searchable at once: its Bloom filter is built on the device from `seqs` at the parameters of
+        group `group` (kwage_bloom_bits_from_batch: the exact k-mer set), inserted into that group's resident matrix
+        (Group.insert_filters) and recorded under `accession` in a live block of the group's layout, whose path is "live".
+        Returns (group index, column).  The group needs room: FileDatabase(..., headroom=n)."""
+        g = self.groups[group]
+        bits = np.zeros((1, max(1, (1 << g.params.log_2_filter_len) // 8)), dtype=np.uint8)
+        b = Batch(self.ctx, seqs)
+        try:
+            distinct = C.c_uint64()
+            check(lib().kwage_bloom_bits_from_batch(self.ctx._h, C.byref(g.params), b._h, bits.ctypes.data, C.byref(distinct)))
+        finally:
+            b.close()
+        col = g.insert_filters(bits)
+        self._layout[group].append((col, 1, _LiveBlock([accession])))
+        return group, col
+
+    def retire_sample(self, accession: str) -> Tuple[int, int]:
+        """Withdraw the first sample (in report order) carrying the run accession: Group.retire_columns on its column.
+        Returns (group index, column); KeyError when no sample carries it."""
+        for gi, col, path, c in self._samples():
+            if self._accession(path, c) == accession:
+                break
+        else:
+            raise KeyError("no sample with run accession %s in the database" % accession)
+        self.groups[gi].retire_columns([col])
+        if isinstance(path, _LiveBlock):
+            self._layout[gi] = [e for e in self._layout[gi] if e[2] is not path]
+        else:
+            self._retired.add((gi, col))
+        return gi, col
 
     def _accession(self, path: str, column: int) -> str:
+        if isinstance(path, _LiveBlock):
+            return path.accessions[column]
         d = self._info.get(path)
         if d is None:
             d = C.c_void_p()
@@ -818,32 +929,29 @@ class FileDatabase(Database):
         b = Batch(self.ctx, seqs)
         per_query = {}
         try:
-            for g, layout in zip(self.groups, self._layout):
+            for gi, (g, layout) in enumerate(zip(self.groups, self._layout)):
                 r = search_topk(g, b, k, threshold)
                 starts = [f[0] for f in layout]
                 for q, c, m in r.hits.tolist():
                     i = bisect.bisect_right(starts, c) - 1
                     first, _, path = layout[i]
-                    per_query.setdefault(q, []).append((m, path, c - first, int(r.num_query_kmer[q])))
+                    per_query.setdefault(q, []).append((m, path, c - first, int(r.num_query_kmer[q]), gi, c))
         finally:
             b.close()
         out: List[DatabaseHit] = []
         for q in sorted(per_query):
-            best = sorted(per_query[q], key=lambda h: (-h[0], order[h[1]], h[2]))[:k]
-            out.extend(DatabaseHit(q, path, col, self._accession(path, col), m, nk) for m, path, col, nk in best)
+            # (live samples rank behind every file, group by group in column order)
+            best = sorted(per_query[q], key=lambda h: (-h[0], len(order) + h[4], h[5]) if isinstance(h[1], _LiveBlock) else (-h[0], order[h[1]], h[2]))[:k]
+            out.extend(DatabaseHit(q, path, col, self._accession(path, col), m, nk) for m, path, col, nk, _, _ in best)
         return out
 
     def score_matrix(self, seqs: Sequence[bytes | str]) -> Tuple[np.ndarray, List[str]]:
         """What `kwage_scores -d ... <seqs>` prints, as (uint32 [n_queries, n_samples], run accessions): the real columns
-        only, in file order then column order."""
-        where = {path: (base, first, nf) for base, layout in zip(np.cumsum([0] + [g.column_span for g in self.groups]), self._layout)
-                 for first, nf, path in layout}
-        cols, accessions = [], []
-        for f in self.files:
-            base, first, nf = where[f]
-            cols.append(int(base) + first + np.arange(nf, dtype=np.int64))
-            accessions.extend(self._accession(f, c) for c in range(nf))
-        cols = np.concatenate(cols) if cols else np.zeros(0, np.int64)
+        only, in file order then column order (live samples behind the files, retired ones left out)."""
+        bases = np.cumsum([0] + [g.column_span for g in self.groups])
+        samples = self._samples()
+        cols = np.array([int(bases[gi]) + col for gi, col, _, _ in samples], dtype=np.int64)
+        accessions = [self._accession(path, c) for _, _, path, c in samples]
         b = Batch(self.ctx, seqs)
         try:
             full = self.search_scores(b).cpu().numpy().view(np.uint32) if self.groups else np.zeros((b.n, 0), np.uint32)
@@ -853,8 +961,7 @@ class FileDatabase(Database):
 
     def presence_matrix(self, seqs: Sequence[bytes | str], threshold: float = 1.0) -> Tuple[np.ndarray, List[str]]:
         """What `kwage_presence -t <threshold> -d ... <seqs>` prints, as (bool [n_queries, n_samples], run accessions):
-        the real columns only, in file order then column order."""
-        cols, accessions = [], []
+        the real columns only, in file order then column order (live samples behind the files, retired ones left out)."""
         b = Batch(self.ctx, seqs)
         try:
             if self.groups:
@@ -864,12 +971,9 @@ class FileDatabase(Database):
                 full, bases = np.zeros((b.n, 0), dtype=bool), []
         finally:
             b.close()
-        where = {path: (base, first, nf) for base, layout in zip(bases, self._layout) for first, nf, path in layout}
-        for f in self.files:
-            base, first, nf = where[f]
-            cols.append(int(base) + first + np.arange(nf, dtype=np.int64))
-            accessions.extend(self._accession(f, c) for c in range(nf))
-        cols = np.concatenate(cols) if cols else np.zeros(0, np.int64)
+        samples = self._samples()
+        cols = np.array([int(bases[gi]) + col for gi, col, _, _ in samples], dtype=np.int64)
+        accessions = [self._accession(path, c) for _, _, path, c in samples]
         return np.ascontiguousarray(full[:, cols]), accessions
 
     def similar_samples(self, accessions: Sequence[str], k: int) -> List[Tuple[str, List[Tuple[str, str, int, int, int, int, float]]]]:
@@ -877,15 +981,9 @@ class FileDatabase(Database):
         is the first (file, column) carrying it, in file order; one not found raises KeyError.  Returns
         [(accession, [(sample accession, path, column in the file, shared, query_bits, sample_bits, jaccard), ...]), ...]."""
         import bisect
-        where = {}
-        for gi, layout in enumerate(self._layout):
-            for first, nf, path in layout:
-                where[path] = (gi, first, nf)
         found = {}
-        for f in self.files:
-            gi, first, nf = where[f]
-            for c in range(nf):
-                found.setdefault(self._accession(f, c), (gi, first + c))
+        for gi, col, path, c in self._samples():
+            found.setdefault(self._accession(path, c), (gi, col))
         for a in accessions:
             if a not in found:
                 raise KeyError("no sample with run accession %s in the database" % a)

@@ -132,6 +132,10 @@ _SIGNATURES = [
     ("kwage_group_device_bytes", C.c_uint64, [_P]),
     ("kwage_group_placement", C.c_int, [_P, C.POINTER(C.c_uint32), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     ("kwage_group_params", C.c_int, [_P, C.POINTER(Params)]),
+    ("kwage_group_insert_filters", C.c_int, [_P, _P, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_float)]),
+    ("kwage_group_insert_filters_device", C.c_int, [_P, _P, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_float)]),
+    ("kwage_group_insert_bloom_files", C.c_int, [_P, C.POINTER(C.c_char_p), C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_float)]),
+    ("kwage_group_retire_columns", C.c_int, [_P, _P, C.c_uint64]),
     ("kwage_batch_create", C.c_int, [_P, C.c_char_p, _P, C.c_uint32, C.POINTER(_P)]),
     ("kwage_batch_destroy", None, [_P]),
     ("kwage_batch_num_queries", C.c_uint32, [_P]),
