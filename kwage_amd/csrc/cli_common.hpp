@@ -1,8 +1,10 @@
-// kwage_amd/csrc/cli_common.hpp -- what the two command-line programs share: `kwage` (kwage_main.cpp, one process) and
-// `kwage_node` (kwage_node.cpp, one process per GPU).  The option surface of the reference (options.cpp:39-192), the
-// query sources (kwage.cpp:116-148), the hit records the report is made from, and the CSV / JSON report writers
-// (output.h:35-112) live here ONCE, so the two programs cannot drift apart: same options, same bytes.
-// Included by exactly those two translation units (everything is in an unnamed namespace).
+// kwage_amd/csrc/cli_common.hpp -- what all the command-line programs share: `kwage` (kwage_main.cpp), `kwage_node`,
+// `kwage_top`, `kwage_top_node`, `kwage_scores`, `kwage_presence` and `kwage_near`.  The option surface of the reference
+// (options.cpp:39-192) and ONE reader for it that every program drives with a description of its own (CliSpec); the query
+// sources (kwage.cpp:116-148), the hit records the report is made from, and the CSV / JSON report writers
+// (output.h:35-112); and what every program does around its search: the output stream, the database files' headers, the
+// report, the ladder of catch clauses.  Each exists ONCE, so the programs cannot drift apart: same options, same bytes.
+// Every program is one translation unit that includes this file (everything is in an unnamed namespace).
 #ifndef KWAGE_AMD_CLI_COMMON_HPP
 #define KWAGE_AMD_CLI_COMMON_HPP
 #include <algorithm>
@@ -15,6 +17,7 @@
 #include <deque>
 #include <exception>
 #include <fstream>
+#include <functional>
 #include <iostream>
 #include <map>
 #include <memory>
@@ -54,6 +57,8 @@ struct Cli {
 	float threshold = 1.0f;                     // reference options.h:148
 	Format format = JSON;
 	bool show_usage = false;
+	uint32_t k = 0;                             // -k, where the program has one
+	vector<string> accessions;                  // -s and the positional arguments, where the program has -s
 };
 
 // One row per flag: how getopt sees it and what it does.  Long-only flags get codes above the char range.
@@ -73,16 +78,6 @@ const FlagSpec FLAG_TABLE[] = {
 	{'?', nullptr, false, [](Cli &c, const char *) { c.show_usage = true; }},             // also what getopt reports for anything unknown
 	{256, "o.csv", false, [](Cli &c, const char *) { c.format = Cli::CSV; }},
 	{257, "o.json", false, [](Cli &c, const char *) { c.format = Cli::JSON; }},
-};
-
-const char *const USAGE_LINES[] = {
-	"Usage for KWAGE (v. 0.4d):",                                   // version string of reference kwage.h:4
-	"\t[-o <output file>] (default is stdout)",
-	"\t[--o.csv (output CSV) | --o.json (output JSON)]",
-	"\t[-t <search threshold>] (default is 1)",
-	"\t-d <database search path> (can be repeated)",
-	"\t[-i <input sequence file>] (can be repeated)",
-	"\t[<DNA sequence>] (can be repeated)",
 };
 
 const char *const QUERY_SUFFIXES[] = {".fna", ".fna.gz", ".fasta", ".fasta.gz", ".fa", ".fa.gz", ".fastq", ".fastq.gz"};
@@ -130,43 +125,134 @@ void find_database_files(const vector<string> &roots, vector<string> &out_db)
 	}
 }
 
-// Parse argv into `cli` and the list of database files.  Returns false when the program should stop
-// (usage shown or a complaint printed) -- with exit status 0, like the reference.
-bool read_command_line(int argc, char *argv[], Cli &cli, vector<string> &db_files)
+// -k's value: decimal digits only, 1 .. KWAGE_TOPK_MAX.  Returns the complaint, or an empty string.
+string parse_k(const char *text, uint32_t &k)
 {
-	string shorts;
+	if(!text){ return "Please provide the number of samples per query (-k)"; }
+	const string s(text);
+	const bool digits = !s.empty() && s.size() <= 9 && all_of(s.begin(), s.end(), [](char c) { return c >= '0' && c <= '9'; });
+	const unsigned long v = digits ? strtoul(s.c_str(), nullptr, 10) : 0;
+	if(!digits || v < 1 || v > KWAGE_TOPK_MAX){
+		return "Please provide: 1 <= -k <= " + to_string(KWAGE_TOPK_MAX) + " (got \"" + s + "\")";
+	}
+	k = (uint32_t)v;
+	return string();
+}
+
+// What can be wrong with a command line (WALK_DB is no complaint: it walks the -d paths and may throw).  A program checks
+// them in the order its CliSpec lists them; the first that applies ends the run.
+enum Complaint { WALK_DB, NO_DB, NO_QUERY, BAD_QUERY_NAME, BAD_THRESHOLD, BAD_K, NO_ACCESSION };
+
+// One program's command line, for read_command_line.
+struct CliSpec {
+	vector<const char*> usage;
+	const char *flags;                  // the short flags of FLAG_TABLE it takes besides -h; any other flag shows the usage text
+	bool formats;                       // --o.csv and --o.json
+	bool has_k;                         // -k <n>, into Cli::k ...
+	const char *k_default;              // ... with this text when it is not given (null: -k is required)
+	bool has_s;                         // -s <accession>: those and the positional arguments are Cli::accessions, not query_seqs
+	float threshold;                    // what -t starts from
+	bool t_zero, t_nan;                 // BAD_THRESHOLD: -t must lie in (0, 1], with t_zero in [0, 1]; t_nan lets a NaN pass, as
+	                                    // the reference's `t <= 0 || t > 1` does
+	int bare_status, refused_status;    // how the usage text ends the run: without arguments; after a flag that is not taken (-h: 0)
+	int complaint_status;
+	vector<Complaint> order;
+};
+
+const CliSpec KWAGE_CLI = {
+	{
+		"Usage for KWAGE (v. 0.4d):",                                   // version string of reference kwage.h:4
+		"\t[-o <output file>] (default is stdout)",
+		"\t[--o.csv (output CSV) | --o.json (output JSON)]",
+		"\t[-t <search threshold>] (default is 1)",
+		"\t-d <database search path> (can be repeated)",
+		"\t[-i <input sequence file>] (can be repeated)",
+		"\t[<DNA sequence>] (can be repeated)",
+	},
+	"odit", true,                                       // every flag of FLAG_TABLE
+	false, nullptr, false,                              // no -k, no -s
+	1.0f, false, true,                                  // -t: 1 unless given, (0, 1], tested as the reference tests it
+	EXIT_SUCCESS, EXIT_SUCCESS, EXIT_SUCCESS,           // (the reference ends every such run with 0)
+	{WALK_DB, NO_DB, NO_QUERY, BAD_QUERY_NAME, BAD_THRESHOLD},
+};
+
+// Parse argv into `cli` and the list of database files as `spec` describes.  Every complaint is reported before a device
+// is touched; returns the exit status to end with (usage shown or a complaint printed), or -1 to go on.
+int read_command_line(const CliSpec &spec, int argc, char *argv[], Cli &cli, vector<string> &db_files)
+{
+	string shorts = string(spec.has_k ? "k:" : "") + (spec.has_s ? "s:" : "");
 	vector<struct option> longs;
 	for(const FlagSpec &f : FLAG_TABLE){
-		if(f.long_name){ longs.push_back({f.long_name, f.takes_value ? required_argument : no_argument, nullptr, f.code}); }
-		else{ shorts += (char)f.code; if(f.takes_value){ shorts += ':'; } }
+		if(f.long_name){
+			if(spec.formats){ longs.push_back({f.long_name, f.takes_value ? required_argument : no_argument, nullptr, f.code}); }
+		}
+		else if(f.code == 'h' || f.code == '?' || strchr(spec.flags, f.code)){ shorts += (char)f.code; if(f.takes_value){ shorts += ':'; } }
 	}
 	longs.push_back({nullptr, 0, nullptr, 0});
 	opterr = 0;
+	cli.threshold = spec.threshold;
 	cli.show_usage = (argc == 1);
+	bool refused = false;
+	const char *k_text = spec.k_default;
 	for(int code; (code = getopt_long(argc, argv, shorts.c_str(), longs.data(), nullptr)) != -1; ){
+		if(spec.has_k && code == 'k'){ k_text = optarg; continue; }
+		if(spec.has_k && code == '?' && optopt == 'k'){ k_text = ""; continue; }       // -k without its value
+		if(spec.has_s && code == 's'){ cli.accessions.push_back(optarg); continue; }
+		if(code == '?'){ refused = true; }
 		const FlagSpec *f = find_if(begin(FLAG_TABLE), end(FLAG_TABLE), [&](const FlagSpec &x) { return x.code == code; });
 		if(f != end(FLAG_TABLE)){ f->apply(cli, optarg); }
 	}
 	if(cli.show_usage){
-		for(const char *line : USAGE_LINES){ cerr << line << endl; }
-		return false;
+		for(const char *line : spec.usage){ cerr << line << endl; }
+		return argc == 1 ? spec.bare_status : (refused ? spec.refused_status : EXIT_SUCCESS);
 	}
-	cli.query_seqs.assign(argv + optind, argv + argc);          // getopt has moved the non-options to the end
-	find_database_files(cli.db_roots, db_files);
+	vector<string> &positional = spec.has_s ? cli.accessions : cli.query_seqs;
+	positional.insert(positional.end(), argv + optind, argv + argc);          // getopt has moved the non-options to the end
 
 	const string *bad_name = nullptr;
 	for(const string &q : cli.query_files){ if(!bad_name && !accepted_query_name(q)){ bad_name = &q; } }
-	// complaints in the reference's order; the first that applies ends the run
-	const struct { bool failed; string text; } checks[] = {
-		{db_files.empty(), "Please provide at least one database file to search (-d)"},
-		{cli.query_files.empty() && cli.query_seqs.empty(), "Please provide at least one query sequence or file"},
-		{bad_name != nullptr, "The query sequence file name, " + (bad_name ? *bad_name : string()) + ", does not have an allowed file extension"},
-		{(cli.threshold <= 0.0) || (cli.threshold > 1.0), "Please provide: 0.0 < search threshold <= 1.0"},
-	};
-	for(const auto &c : checks){
-		if(c.failed){ cerr << c.text << endl; return false; }
+	const float t = cli.threshold;
+	const bool bad_t = (t != t) ? !spec.t_nan : (t > 1.0f || (spec.t_zero ? t < 0.0f : t <= 0.0f));
+	for(Complaint c : spec.order){
+		string text;
+		switch(c){
+		case WALK_DB: find_database_files(cli.db_roots, db_files); break;
+		case NO_DB: if(db_files.empty()){ text = "Please provide at least one database file to search (-d)"; } break;
+		case NO_QUERY: if(cli.query_files.empty() && cli.query_seqs.empty()){ text = "Please provide at least one query sequence or file"; } break;
+		case BAD_QUERY_NAME: if(bad_name){ text = "The query sequence file name, " + *bad_name + ", does not have an allowed file extension"; } break;
+		case BAD_THRESHOLD: if(bad_t){ text = string("Please provide: 0.0 ") + (spec.t_zero ? "<=" : "<") + " search threshold <= 1.0"; } break;
+		case BAD_K: text = parse_k(k_text, cli.k); break;
+		case NO_ACCESSION: if(cli.accessions.empty()){ text = "Please provide at least one run accession of a sample of the database"; } break;
+		}
+		if(!text.empty()){ cerr << text << endl; return spec.complaint_status; }
 	}
-	return true;
+	return -1;
+}
+
+// A program's body under the one ladder of catch clauses: its exit status, or EXIT_FAILURE and what was thrown on stderr.
+template<class Body> int guarded(Body body)
+{
+	try{ return body(); }
+	catch(const char *error){
+		cerr << "Caught the error " << error << endl;
+	}
+	catch(const string &error){
+		cerr << "Caught the error " << error << endl;
+	}
+	catch(...){
+		cerr << "Caught an unhandled error" << endl;
+	}
+	return EXIT_FAILURE;
+}
+
+// Where the output goes: `file`, opened for -o's path, or stdout when there is none.  False: the file cannot be opened
+// (said on stderr).  Afterwards the stream is `file.is_open() ? file : cout`.
+bool open_output(const string &path, ofstream &file)
+{
+	if(path.empty()){ return true; }
+	file.open(path.c_str());
+	if(!file){ cerr << "Unable to open " << path << " for writing" << endl; }
+	return (bool)file;
 }
 
 // =====================================================================================================
@@ -339,6 +425,26 @@ struct DbFileEntry {
 void check(int rc)
 {
 	if(rc != KWAGE_OK){ throw string(kwage_last_error()); }
+}
+
+// The header of every database file and, where `infos` is given, its metadata index, read once (kwage.cpp:89-113,
+// 505-515).  `complain`: what went wrong goes to stderr before the throw (the ranks of a node leave that to rank 0).
+void read_database_files(const vector<string> &db_paths, vector<DbFileEntry> &files, vector<DbInfo> *infos, bool complain = true)
+{
+	files.resize(db_paths.size());
+	if(infos){ vector<DbInfo>(db_paths.size()).swap(*infos); }          // (a DbInfo cannot be moved)
+	for(size_t i = 0; i < db_paths.size(); ++i){
+		files[i].path = db_paths[i];
+		if(kwage_db_read_header(files[i].path.c_str(), &files[i].header) != KWAGE_OK){
+			if(complain){ cerr << kwage_last_error() << endl; }
+			throw "main: I/O error";
+		}
+		string err;
+		if(infos && !(*infos)[i].open(files[i].path, err)){
+			cerr << err << endl;
+			throw "main: Unable to read header";
+		}
+	}
 }
 
 // =====================================================================================================
@@ -522,6 +628,30 @@ struct JsonReport : Report {
 	}
 	void end() override { if(js){ js->finish(); } to.flush(); to.out.flush(); }
 };
+
+// Each query's hits in the order the single-threaded reference collects them (file order, then column), then its unstable
+// descending sort by hits (kwage.cpp:191-201); then the report in the format `cli` asks for: the command-line queries
+// first, by position (kwage.cpp:237-240), then the file queries by global id.  `ordered` is called between the two.
+void write_report(const Cli &cli, ostream &out, const vector<DbInfo> &infos, Findings &from_command_line, Findings &from_files,
+                  const function<void()> &ordered = nullptr)
+{
+	for(Findings *f : {&from_command_line, &from_files}){
+		for(auto &kv : f->by_query){
+			sort(kv.second.begin(), kv.second.end(), [](const Match &a, const Match &b) {
+				return (a.file_index != b.file_index) ? (a.file_index < b.file_index) : (a.column < b.column);
+			});
+			sort(kv.second.begin(), kv.second.end(), [](const Match &a, const Match &b) { return a.num_kmers_found > b.num_kmers_found; });
+		}
+	}
+	if(ordered){ ordered(); }
+	unique_ptr<Report> report;
+	if(cli.format == Cli::CSV){ report.reset(new CsvReport(out, infos)); }
+	else{ report.reset(new JsonReport(out, cli.threshold, infos)); }
+	report->begin(from_command_line.by_query.size() + from_files.by_query.size());
+	for(const auto &kv : from_command_line.by_query){ report->query("command line seq " + to_string(kv.first), kv.second); }
+	for(const auto &kv : from_files.by_query){ report->query(from_files.defline[kv.first], kv.second); }
+	report->end();
+}
 
 uint64_t env_u64(const char *name, uint64_t fallback)
 {

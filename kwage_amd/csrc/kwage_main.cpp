@@ -336,39 +336,20 @@ int main(int argc, char *argv[])
 	// two search streams per device context plus the loader's: keep them on hardware queues of their own
 	// (HIP's default is 4 queues per device for all streams of the process); an explicit setting wins
 	setenv("GPU_MAX_HW_QUEUES", "8", 0);
-	try{
+	return guarded([&]() -> int {
 		const time_t started = time(nullptr);
 		const double t_main = now_s();
 
 		Cli cli;
 		vector<string> db_paths;
-		if(!read_command_line(argc, argv, cli, db_paths)){ return EXIT_SUCCESS; }
-
+		const int status = read_command_line(KWAGE_CLI, argc, argv, cli, db_paths);
+		if(status >= 0){ return status; }
 		ofstream fout;
-		if(!cli.output_path.empty()){
-			fout.open(cli.output_path.c_str());
-			if(!fout){
-				cerr << "Unable to open " << cli.output_path << " for writing" << endl;
-				return EXIT_FAILURE;
-			}
-		}
+		if(!open_output(cli.output_path, fout)){ return EXIT_FAILURE; }
 		ostream &out = fout.is_open() ? fout : cout;
-
-		// ---- headers + metadata of every database file, read once (kwage.cpp:89-113, 505-515) ------------
-		vector<DbFileEntry> files(db_paths.size());
-		vector<DbInfo> infos(db_paths.size());
-		for(size_t i = 0; i < db_paths.size(); ++i){
-			files[i].path = db_paths[i];
-			if(kwage_db_read_header(files[i].path.c_str(), &files[i].header) != KWAGE_OK){
-				cerr << kwage_last_error() << endl;
-				throw "main: I/O error";
-			}
-			string err;
-			if(!infos[i].open(files[i].path, err)){
-				cerr << err << endl;
-				throw "main: Unable to read header";
-			}
-		}
+		vector<DbFileEntry> files;
+		vector<DbInfo> infos;
+		read_database_files(db_paths, files, &infos);
 
 		// ---- files grouped by (k, hashes, log2 length, hash function): one HBM matrix per group ------------
 		struct GroupKey {
@@ -823,29 +804,8 @@ int main(int argc, char *argv[])
 		}
 
 		const double t_searched = now_s();
-		// ---- order: each query's hits as the single-threaded reference collects them (file order, then
-		// column), then its unstable descending sort by hits (kwage.cpp:191-201) -------------------------------
-		for(Findings *f : {&from_command_line, &from_files}){
-			for(auto &kv : f->by_query){
-				sort(kv.second.begin(), kv.second.end(), [](const Match &a, const Match &b) {
-					return (a.file_index != b.file_index) ? (a.file_index < b.file_index) : (a.column < b.column);
-				});
-				sort(kv.second.begin(), kv.second.end(), [](const Match &a, const Match &b) { return a.num_kmers_found > b.num_kmers_found; });
-			}
-		}
-
-		const double t_ordered = now_s();
-		unique_ptr<Report> report;
-		if(cli.format == Cli::CSV){ report.reset(new CsvReport(out, infos)); }
-		else{ report.reset(new JsonReport(out, cli.threshold, infos)); }
-		report->begin(from_command_line.by_query.size() + from_files.by_query.size());
-		for(const auto &kv : from_command_line.by_query){                       // command-line queries first, by position
-			report->query("command line seq " + to_string(kv.first), kv.second);     // kwage.cpp:237-240
-		}
-		for(const auto &kv : from_files.by_query){                              // then file queries by global id
-			report->query(from_files.defline[kv.first], kv.second);
-		}
-		report->end();
+		double t_ordered = t_searched;
+		write_report(cli, out, infos, from_command_line, from_files, [&]() { t_ordered = now_s(); });
 		if(verbose){
 			cerr << "[kwage] workers done " << (t_searched - t_main) << " s after the start of main; hits ordered in " << (t_ordered - t_searched)
 			     << " s, report written in " << (now_s() - t_ordered) << " s; " << rss_mb() << endl;
@@ -853,18 +813,6 @@ int main(int argc, char *argv[])
 
 		if(verbose){ cerr << "[kwage] " << (now_s() - t_main) << " s from the start of main to its last statement" << endl; }
 		cerr << "Search complete in " << (time(nullptr) - started) << " sec" << endl;
-	}
-	catch(const char *error){
-		cerr << "Caught the error " << error << endl;
-		return EXIT_FAILURE;
-	}
-	catch(const string &error){
-		cerr << "Caught the error " << error << endl;
-		return EXIT_FAILURE;
-	}
-	catch(...){
-		cerr << "Caught an unhandled error" << endl;
-		return EXIT_FAILURE;
-	}
-	return EXIT_SUCCESS;
+		return EXIT_SUCCESS;
+	});
 }

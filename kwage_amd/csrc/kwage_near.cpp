@@ -1,7 +1,7 @@
 // kwage_amd/csrc/kwage_near.cpp -- the `kwage_near` command-line program: for samples of the database, named by run
 // accession, the k samples whose Bloom filters are most like theirs, by Jaccard index of the set rows (the filter search,
-// kwage_search_filter_scores).  No counterpart in the reference.  The options are kwage's -d and -o (cli_common.hpp),
-// -k (top_common.hpp's parser; default 10) and the accessions, positional or with -s.
+// kwage_search_filter_scores).  No counterpart in the reference.  The options are kwage's -d and -o, -k (default 10) and
+// the accessions, positional or with -s (cli_common.hpp's reader).
 //
 //   query <TAB> rank <TAB> sample <TAB> shared_bits <TAB> query_bits <TAB> sample_bits <TAB> jaccard
 //
@@ -17,49 +17,28 @@
 // reached.  Files whose Bloom parameters differ from a query sample's are skipped for that sample: filters built
 // differently are not comparable.
 //
-// Environment: KWAGE_DEVICE (HIP device index, default 0).
-#include "top_common.hpp"
+// Environment: KWAGE_DEVICE (file_search.hpp).
+#include "file_search.hpp"
 
 namespace {
 
-const char *const NEAR_USAGE_LINES[] = {
-	"Usage for kwage_near (the samples most like given samples of the database, by Jaccard index of their Bloom filters):",
-	"\t[-k <number of samples per query sample>] (1 to 1024, default is 10)",
-	"\t[-o <output file>] (default is stdout)",
-	"\t-d <database search path> (can be repeated)",
-	"\t[-s <run accession>] (can be repeated)",
-	"\t[<run accession>] (can be repeated)",
+// kwage's -o, -d and -h, plus -k and -s; anything else shows the usage text
+const CliSpec NEAR_CLI = {
+	{
+		"Usage for kwage_near (the samples most like given samples of the database, by Jaccard index of their Bloom filters):",
+		"\t[-k <number of samples per query sample>] (1 to 1024, default is 10)",
+		"\t[-o <output file>] (default is stdout)",
+		"\t-d <database search path> (can be repeated)",
+		"\t[-s <run accession>] (can be repeated)",
+		"\t[<run accession>] (can be repeated)",
+	},
+	"od", false,
+	true, "10", true,                                   // -k, 10 unless given; -s
+	1.0f, false, false,                                 // (no -t)
+	EXIT_FAILURE, EXIT_FAILURE, EXIT_FAILURE,
+	{BAD_K, NO_ACCESSION, WALK_DB, NO_DB},
 };
-
-// kwage's -o, -d and -h out of FLAG_TABLE, plus -k and -s; anything else shows the usage text.  Every complaint is
-// reported before a device is touched; returns the exit status to end with, or -1 to go on.
-int read_near_command_line(int argc, char *argv[], Cli &cli, uint32_t &k, vector<string> &accessions, vector<string> &db_files)
-{
-	const struct option longs[] = {{nullptr, 0, nullptr, 0}};
-	opterr = 0;
-	cli.show_usage = (argc == 1);
-	bool refused = false;
-	const char *k_text = "10";
-	for(int code; (code = getopt_long(argc, argv, "k:s:o:d:h", longs, nullptr)) != -1; ){
-		if(code == 'k'){ k_text = optarg; continue; }
-		if(code == 's'){ accessions.push_back(optarg); continue; }
-		if(code == '?' && optopt == 'k'){ k_text = ""; continue; }       // -k without its value
-		if(code == '?'){ refused = true; }
-		const FlagSpec *f = find_if(begin(FLAG_TABLE), end(FLAG_TABLE), [&](const FlagSpec &x) { return x.code == code; });
-		if(f != end(FLAG_TABLE)){ f->apply(cli, optarg); }
-	}
-	if(cli.show_usage){
-		for(const char *line : NEAR_USAGE_LINES){ cerr << line << endl; }
-		return (argc == 1 || refused) ? EXIT_FAILURE : EXIT_SUCCESS;
-	}
-	const string k_err = parse_k(k_text, k);
-	if(!k_err.empty()){ cerr << k_err << endl; return EXIT_FAILURE; }
-	accessions.insert(accessions.end(), argv + optind, argv + argc);
-	if(accessions.empty()){ cerr << "Please provide at least one run accession of a sample of the database" << endl; return EXIT_FAILURE; }
-	find_database_files(cli.db_roots, db_files);
-	if(db_files.empty()){ cerr << "Please provide at least one database file to search (-d)" << endl; return EXIT_FAILURE; }
-	return -1;
-}
+static_assert(KWAGE_TOPK_MAX == 1024u, "NEAR_CLI's usage text quotes the cap");
 
 struct Near {
 	double jaccard;
@@ -92,47 +71,29 @@ bool same_params(const kwage_db_header &a, const kwage_db_header &b)
 	return a.kmer_len == b.kmer_len && a.num_hash == b.num_hash && a.log_2_filter_len == b.log_2_filter_len && a.hash_func == b.hash_func;
 }
 
-// One file as a finalized group of its own.
-kwage_group *load_file(kwage_ctx *ctx, const DbFileEntry &f, uint64_t &first)
-{
-	const kwage_db_header &h = f.header;
-	kwage_params p{h.kmer_len, h.num_hash, h.log_2_filter_len, h.hash_func};
-	kwage_group *g = nullptr;
-	check(kwage_group_create(ctx, &p, h.num_filter, &g));
-	try{
-		uint32_t nf = 0;
-		check(kwage_group_add_db_file(g, f.path.c_str(), &first, &nf));
-		check(kwage_group_finalize(g));
-	}
-	catch(...){ kwage_group_destroy(g); throw; }
-	return g;
-}
+// The sets' row lists on the device, destroyed with this object.
+struct SetsOnDevice {
+	vector<SourceSet> &sets;
+	~SetsOnDevice() { for(SourceSet &s : sets){ kwage_filterset_destroy(s.fs); } }
+};
 
 }  // namespace
 
 int main(int argc, char *argv[])
 {
-	try{
+	return guarded([&]() -> int {
 		Cli cli;
-		uint32_t k = 10;
-		vector<string> db_paths, accessions;
-		const int status = read_near_command_line(argc, argv, cli, k, accessions, db_paths);
+		vector<string> db_paths;
+		const int status = read_command_line(NEAR_CLI, argc, argv, cli, db_paths);
 		if(status >= 0){ return status; }
+		const uint32_t k = cli.k;
+		const vector<string> &accessions = cli.accessions;
 
-		vector<DbFileEntry> files(db_paths.size());
-		vector<DbInfo> infos(db_paths.size());
+		vector<DbFileEntry> files;
+		vector<DbInfo> infos;
+		read_database_files(db_paths, files, &infos);
 		vector<vector<string>> names(db_paths.size());          // run accession of every column
-		for(size_t i = 0; i < db_paths.size(); ++i){
-			files[i].path = db_paths[i];
-			if(kwage_db_read_header(files[i].path.c_str(), &files[i].header) != KWAGE_OK){
-				cerr << kwage_last_error() << endl;
-				throw "main: I/O error";
-			}
-			string err;
-			if(!infos[i].open(files[i].path, err)){
-				cerr << err << endl;
-				throw "main: Unable to read header";
-			}
+		for(size_t i = 0; i < files.size(); ++i){
 			names[i].resize(files[i].header.num_filter);
 			for(uint32_t c = 0; c < files[i].header.num_filter; ++c){
 				FilterInfo info;
@@ -168,33 +129,21 @@ int main(int argc, char *argv[])
 		sort(sets.begin(), sets.end(), [](const SourceSet &a, const SourceSet &b) { return a.file < b.file; });
 
 		ofstream fout;
-		if(!cli.output_path.empty()){
-			fout.open(cli.output_path.c_str());
-			if(!fout){
-				cerr << "Unable to open " << cli.output_path << " for writing" << endl;
-				return EXIT_FAILURE;
-			}
-		}
+		if(!open_output(cli.output_path, fout)){ return EXIT_FAILURE; }
 		ostream &out = fout.is_open() ? fout : cout;
 
-		kwage_ctx *ctx = nullptr;
-		check(kwage_init((int)env_u64("KWAGE_DEVICE", 0), &ctx));
-		one_shot_placement(ctx);
-		try{
+		{
+			Device device;                              // (declared first: shut down last)
+			SetsOnDevice on_device{sets};
 			// ---- first pass: the source files, their query samples' row lists kept on the device -----------------------------
 			for(SourceSet &s : sets){
-				uint64_t first = 0;
-				kwage_group *g = load_file(ctx, files[s.file], first);
-				try{
-					vector<uint64_t> cols;
-					for(uint32_t q : s.queries){ cols.push_back(first + queries[q].column); }
-					check(kwage_filterset_from_columns(g, cols.data(), (uint32_t)cols.size(), &s.fs));
-					vector<uint32_t> bits(cols.size());
-					check(kwage_filterset_bit_counts(s.fs, bits.data()));
-					for(size_t i = 0; i < cols.size(); ++i){ queries[s.queries[i]].bits = bits[i]; }
-				}
-				catch(...){ kwage_group_destroy(g); throw; }
-				kwage_group_destroy(g);
+				const FileGroup g(device.ctx, files[s.file]);
+				vector<uint64_t> cols;
+				for(uint32_t q : s.queries){ cols.push_back(g.first + queries[q].column); }
+				check(kwage_filterset_from_columns(g.get(), cols.data(), (uint32_t)cols.size(), &s.fs));
+				vector<uint32_t> bits(cols.size());
+				check(kwage_filterset_bit_counts(s.fs, bits.data()));
+				for(size_t i = 0; i < cols.size(); ++i){ queries[s.queries[i]].bits = bits[i]; }
 			}
 			// ---- second pass: every file against every set; each query sample's k best folded on the host ----------------------
 			vector<uint32_t> part, column_bits;
@@ -207,41 +156,29 @@ int main(int argc, char *argv[])
 					}
 				}
 				if(!wanted){ continue; }
-				uint64_t first = 0;
-				kwage_group *g = load_file(ctx, files[fi], first);
-				try{
-					const uint64_t span = kwage_group_column_span(g);
-					const uint32_t nf = files[fi].header.num_filter;
-					column_bits.resize(std::max<uint64_t>(span, 1));
-					check(kwage_group_column_bits(g, column_bits.data()));
-					for(const SourceSet &s : sets){
-						if(!same_params(files[s.file].header, files[fi].header)){ continue; }
-						part.resize(std::max<uint64_t>(s.queries.size()*span, 1));
-						check(kwage_search_filter_scores(g, s.fs, part.data(), span, 0, nullptr));
-						for(size_t i = 0; i < s.queries.size(); ++i){
-							QuerySample &qs = queries[s.queries[i]];
-							for(uint32_t c = 0; c < nf; ++c){
-								const uint64_t shared = part[i*span + first + c], sample_bits = column_bits[first + c];
-								const uint64_t either = (uint64_t)qs.bits + sample_bits - shared;
-								qs.best.push_back(Near{either ? (double)shared/(double)either : 0.0, (uint32_t)fi, c, (uint32_t)shared, (uint32_t)sample_bits});
-							}
-							const size_t keep = std::min<size_t>(k, qs.best.size());
-							partial_sort(qs.best.begin(), qs.best.begin() + (long)keep, qs.best.end(), nearer);
-							qs.best.resize(keep);
+				const FileGroup g(device.ctx, files[fi]);
+				const uint64_t span = kwage_group_column_span(g.get()), first = g.first;
+				const uint32_t nf = files[fi].header.num_filter;
+				column_bits.resize(std::max<uint64_t>(span, 1));
+				check(kwage_group_column_bits(g.get(), column_bits.data()));
+				for(const SourceSet &s : sets){
+					if(!same_params(files[s.file].header, files[fi].header)){ continue; }
+					part.resize(std::max<uint64_t>(s.queries.size()*span, 1));
+					check(kwage_search_filter_scores(g.get(), s.fs, part.data(), span, 0, nullptr));
+					for(size_t i = 0; i < s.queries.size(); ++i){
+						QuerySample &qs = queries[s.queries[i]];
+						for(uint32_t c = 0; c < nf; ++c){
+							const uint64_t shared = part[i*span + first + c], sample_bits = column_bits[first + c];
+							const uint64_t either = (uint64_t)qs.bits + sample_bits - shared;
+							qs.best.push_back(Near{either ? (double)shared/(double)either : 0.0, (uint32_t)fi, c, (uint32_t)shared, (uint32_t)sample_bits});
 						}
+						const size_t keep = std::min<size_t>(k, qs.best.size());
+						partial_sort(qs.best.begin(), qs.best.begin() + (long)keep, qs.best.end(), nearer);
+						qs.best.resize(keep);
 					}
 				}
-				catch(...){ kwage_group_destroy(g); throw; }
-				kwage_group_destroy(g);
 			}
 		}
-		catch(...){
-			for(SourceSet &s : sets){ kwage_filterset_destroy(s.fs); }
-			kwage_shutdown(ctx);
-			throw;
-		}
-		for(SourceSet &s : sets){ kwage_filterset_destroy(s.fs); }
-		kwage_shutdown(ctx);
 
 		TextSink to(out);
 		to.put("query\trank\tsample\tshared_bits\tquery_bits\tsample_bits\tjaccard\n");
@@ -258,18 +195,6 @@ int main(int argc, char *argv[])
 		}
 		to.flush();
 		out.flush();
-	}
-	catch(const char *error){
-		cerr << "Caught the error " << error << endl;
-		return EXIT_FAILURE;
-	}
-	catch(const string &error){
-		cerr << "Caught the error " << error << endl;
-		return EXIT_FAILURE;
-	}
-	catch(...){
-		cerr << "Caught an unhandled error" << endl;
-		return EXIT_FAILURE;
-	}
-	return EXIT_SUCCESS;
+		return EXIT_SUCCESS;
+	});
 }

@@ -190,33 +190,16 @@ struct RankPipeline {
 
 int run_rank(int rank, int n_ranks, Bootstrap *boot, const Cli &cli, const vector<string> &db_paths, Rehearsal *rehearsal)
 {
-	try{
+	return guarded([&]() -> int {
 		const time_t started = time(nullptr);
 		ofstream fout;
-		if(rank == 0 && !cli.output_path.empty()){
-			fout.open(cli.output_path.c_str());
-			if(!fout){
-				cerr << "Unable to open " << cli.output_path << " for writing" << endl;
-				return EXIT_FAILURE;
-			}
-		}
+		if(rank == 0 && !open_output(cli.output_path, fout)){ return EXIT_FAILURE; }
 		ostream &out = fout.is_open() ? fout : cout;
 
 		// ---- headers (every rank) and metadata (rank 0, read on first use) of every database file ---------------------
-		vector<DbFileEntry> files(db_paths.size());
-		vector<DbInfo> infos(rank == 0 ? db_paths.size() : 0);
-		for(size_t i = 0; i < db_paths.size(); ++i){
-			files[i].path = db_paths[i];
-			if(kwage_db_read_header(files[i].path.c_str(), &files[i].header) != KWAGE_OK){
-				if(rank == 0){ cerr << kwage_last_error() << endl; }
-				throw "main: I/O error";
-			}
-			string err;
-			if(rank == 0 && !infos[i].open(files[i].path, err)){
-				cerr << err << endl;
-				throw "main: Unable to read header";
-			}
-		}
+		vector<DbFileEntry> files;
+		vector<DbInfo> infos;
+		read_database_files(db_paths, files, rank == 0 ? &infos : nullptr, rank == 0);
 		vector<NodeGroup> groups = plan_groups(files, n_ranks);
 		// where every file's columns begin in the global numbering (ascending: groups, ranks and files are numbered in order)
 		vector<ColumnBlock> blocks;
@@ -426,39 +409,13 @@ int run_rank(int rank, int n_ranks, Bootstrap *boot, const Cli &cli, const vecto
 
 		if(rank == 0){
 			// order and report exactly as kwage does (kwage_main.cpp; reference kwage.cpp:191-315)
-			for(Findings *f : {&from_command_line_, &from_files_}){
-				for(auto &kv : f->by_query){
-					sort(kv.second.begin(), kv.second.end(), [](const Match &a, const Match &b) {
-						return (a.file_index != b.file_index) ? (a.file_index < b.file_index) : (a.column < b.column);
-					});
-					sort(kv.second.begin(), kv.second.end(), [](const Match &a, const Match &b) { return a.num_kmers_found > b.num_kmers_found; });
-				}
-			}
-			unique_ptr<Report> report;
-			if(cli.format == Cli::CSV){ report.reset(new CsvReport(out, infos)); }
-			else{ report.reset(new JsonReport(out, cli.threshold, infos)); }
-			report->begin(from_command_line_.by_query.size() + from_files_.by_query.size());
-			for(const auto &kv : from_command_line_.by_query){ report->query("command line seq " + to_string(kv.first), kv.second); }
-			for(const auto &kv : from_files_.by_query){ report->query(from_files_.defline[kv.first], kv.second); }
-			report->end();
+			write_report(cli, out, infos, from_command_line_, from_files_);
 			cerr << "Search complete in " << (time(nullptr) - started) << " sec" << endl;
 		}
 		}
 		kwage_shutdown(ctx);
-	}
-	catch(const char *error){
-		cerr << "Caught the error " << error << endl;
-		return EXIT_FAILURE;
-	}
-	catch(const string &error){
-		cerr << "Caught the error " << error << endl;
-		return EXIT_FAILURE;
-	}
-	catch(...){
-		cerr << "Caught an unhandled error" << endl;
-		return EXIT_FAILURE;
-	}
-	return EXIT_SUCCESS;
+		return EXIT_SUCCESS;
+	});
 }
 
 }  // namespace
@@ -470,13 +427,8 @@ int main(int argc, char *argv[])
 	setenv("NCCL_DEBUG_FILE", "/dev/stderr", 0);           // stdout is the report: RCCL's debug lines (NCCL_DEBUG) go to stderr
 	Cli cli;
 	vector<string> db_paths;
-	try{
-		if(!read_command_line(argc, argv, cli, db_paths)){ return EXIT_SUCCESS; }
-	}
-	catch(const char *error){
-		cerr << "Caught the error " << error << endl;
-		return EXIT_FAILURE;
-	}
+	const int status = guarded([&]() { return read_command_line(KWAGE_CLI, argc, argv, cli, db_paths); });
+	if(status >= 0){ return status; }
 	return node_main("kwage_node", db_paths, [&](int rank, int n_ranks, Bootstrap *boot, Rehearsal *rehearsal) {
 		return run_rank(rank, n_ranks, boot, cli, db_paths, rehearsal);
 	});

@@ -164,15 +164,9 @@ vector<vector<Unit> > plan_passes(const vector<NodeGroup> &groups, const vector<
 // KWAGE_NODE_PLAN=1: print the plan for n_ranks ranks and stop -- no device is touched (tests; a dry run before a long job)
 int print_plan(const vector<string> &db_paths, int n_ranks)
 {
-	try{
-		vector<DbFileEntry> files(db_paths.size());
-		for(size_t i = 0; i < db_paths.size(); ++i){
-			files[i].path = db_paths[i];
-			if(kwage_db_read_header(files[i].path.c_str(), &files[i].header) != KWAGE_OK){
-				cerr << kwage_last_error() << endl;
-				throw "main: I/O error";
-			}
-		}
+	return guarded([&]() -> int {
+		vector<DbFileEntry> files;
+		read_database_files(db_paths, files, nullptr);
 		const vector<NodeGroup> groups = plan_groups(files, n_ranks);
 		cout << "{\"ranks\": " << n_ranks << ", \"groups\": [";
 		for(size_t gi = 0; gi < groups.size(); ++gi){
@@ -220,12 +214,8 @@ int print_plan(const vector<string> &db_paths, int n_ranks)
 			cout << "]";
 		}
 		cout << "}" << endl;
-	}
-	catch(const char *error){
-		cerr << "Caught the error " << error << endl;
-		return EXIT_FAILURE;
-	}
-	return EXIT_SUCCESS;
+		return EXIT_SUCCESS;
+	});
 }
 
 // The RCCL communicator of `rank` (not for a rehearsal): rank 0 makes the unique id and leaves it in `boot`, every rank

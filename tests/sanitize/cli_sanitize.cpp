@@ -133,7 +133,7 @@ void option_parser(const string &golden)
 		Cli cli;
 		vector<string> dbs;
 		optind = 1;
-		const bool got = read_command_line((int)args.size(), argv.data(), cli, dbs);
+		const bool got = read_command_line(KWAGE_CLI, (int)args.size(), argv.data(), cli, dbs) < 0;          // (-1: go on)
 		expect(got == want, "command line '" + (args.size() > 1 ? args[1] : string()) + " ...' accepted: " + (got ? "yes" : "no"));
 		if(got && want){ expect(cli.threshold == thr && !dbs.empty(), "threshold and database files parsed"); }
 	};

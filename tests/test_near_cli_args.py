@@ -6,6 +6,7 @@ import subprocess
 
 import pytest
 
+from cli_early_exits import EARLY_EXITS, check_early_exit
 from conftest import GOLDEN
 
 USAGE = ("Usage for kwage_near (the samples most like given samples of the database, by Jaccard index of their Bloom filters):\n"
@@ -56,9 +57,17 @@ def test_kwage_near_usage(kwage_near, tmp_path, args, status):
     (["-d", "empty", "SRR0001000"], "Please provide at least one database file to search (-d)\n"),
     (["-d", BASIC, "SRR0001000", "-s", "NOSUCH42", "SRR0001001"], "No sample with the run accession NOSUCH42 in the database\n"),
     (["-d", BASIC, "srr0001000"], "No sample with the run accession srr0001000 in the database\n"),
+    # an unknown accession is reported before -o is opened
+    (["-d", BASIC, "-o", "no_such_dir/out.txt", "SRR0001000", "NOSUCH42"], "No sample with the run accession NOSUCH42 in the database\n"),
+    (["-d", BASIC, "-k", "0"], "Please provide: 1 <= -k <= 1024 (got \"0\")\n"),                 # -k before the accessions
 ])
 def test_kwage_near_argument_errors(kwage_near, tmp_path, args, text):
     (tmp_path / "empty").mkdir()                       # a database directory without a single .db file
     r = run(kwage_near, args, tmp_path)
     assert r.returncode == 1, r
     assert r.stderr == text and r.stdout == ""
+
+
+@pytest.mark.parametrize("which", EARLY_EXITS)
+def test_kwage_near_ends_before_a_device(kwage_near, tmp_path, which):
+    check_early_exit(kwage_near, which, ["-s", "SRR0001000"], tmp_path)

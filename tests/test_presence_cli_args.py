@@ -5,6 +5,8 @@ import subprocess
 
 import pytest
 
+from cli_early_exits import EARLY_EXITS, check_early_exit
+
 USAGE = ("Usage for kwage_presence (which samples hold each query: a tab-separated 0/1 matrix):\n"
          "\t[-o <output file>] (default is stdout)\n"
          "\t[-t <search threshold>] (default is 1)\n"
@@ -53,9 +55,15 @@ def test_kwage_presence_usage(kwage_presence, tmp_path, args, status):
     (["-t", "0.8", "ACGT"], "Please provide at least one database file to search (-d)\n"),
     (["-d", "db"], "Please provide at least one query sequence or file\n"),
     (["-d", "db", "-t", "0.8", "-i", "reads.txt"], "The query sequence file name, reads.txt, does not have an allowed file extension\n"),
+    (["-t", "0", "-i", "reads.txt", "-d", "db"], BAD_T),                           # the threshold line, not the name line
 ])
 def test_kwage_presence_argument_errors(kwage_presence, tmp_path, args, text):
     (tmp_path / "db").mkdir()                          # a database directory without a single .db file
     r = run(kwage_presence, args, tmp_path)
     assert r.returncode == 1, r
     assert r.stderr == text and r.stdout == ""
+
+
+@pytest.mark.parametrize("which", EARLY_EXITS)
+def test_kwage_presence_ends_before_a_device(kwage_presence, tmp_path, which):
+    check_early_exit(kwage_presence, which, ["-t", "0.8", "ACGT"], tmp_path)

@@ -4,6 +4,8 @@ import subprocess
 
 import pytest
 
+from cli_early_exits import EARLY_EXITS, check_early_exit
+
 USAGE = ("Usage for kwage_scores (every query's match count for every sample, tab-separated):\n"
          "\t[-o <output file>] (default is stdout)\n"
          "\t-d <database search path> (can be repeated)\n"
@@ -52,3 +54,8 @@ def test_kwage_scores_argument_errors(kwage_scores, tmp_path, args, text):
     r = run(kwage_scores, args, tmp_path)
     assert r.returncode == 1, r
     assert r.stderr == text and r.stdout == ""
+
+
+@pytest.mark.parametrize("which", EARLY_EXITS)
+def test_kwage_scores_ends_before_a_device(kwage_scores, tmp_path, which):
+    check_early_exit(kwage_scores, which, ["ACGT"], tmp_path)
