@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN
+from ordered_list_forms import drive_every_kernel_form
 
 pytestmark = pytest.mark.gpu
 
@@ -259,68 +260,9 @@ def test_long_lists_come_back_ordered_from_every_kernel_form(ka, ctx, n_cols):
     other columns, ascending -- narrow kernels (several queries per wave, one reservation per workgroup), the tiled AND
     kernel with 1 / 2 / 4 vectors per lane, its segments + combine pass, the walk form (one and three column tiles,
     natural shares and shares of a few positions), band after band, and the four forms of the count path."""
-    L, k = 6, 31
-    nbytes = (n_cols + 7) // 8
-    col = np.arange(nbytes * 8)
-    bits = ((col % 7 != 3) & (col < n_cols)).astype(np.uint8).reshape(nbytes, 8)
-    row = np.packbits(bits, axis=1, bitorder="little").reshape(-1)
-    image = np.ascontiguousarray(np.tile(row, (1 << L, 1)))
-    one_cols = np.arange(n_cols, dtype=np.uint32)[np.arange(n_cols) % 7 != 3]
-    rng = np.random.default_rng(n_cols)
     n_queries = 200 if n_cols <= 5000 else (90 if n_cols <= 40000 else 24)
-    seqs = []
-    for i in range(n_queries):
-        # (at most 120 k-mers: no automatic row-list segments; at least 3: a threshold that truncates to 0 would report the zero columns too)
-        n = int(rng.choice([33, 35, 40, 64, 100, 150]))
-        seqs.append("ACGT" if i % 9 == 4 else ("N" * n if i % 13 == 5 else rand_seq(rng, n)))
-    g = ka.Group(ctx, k, 2, L, n_cols)
-    g.add_columns(image, n_cols)
-    g.finalize()
-    b = ka.Batch(ctx, seqs)
-
-    def check(r, want_kernel):
-        assert r.search_kernel.startswith(want_kernel), (r.search_kernel, want_kernel)
-        nk = r.num_query_kmer
-        live = np.flatnonzero(nk > 0).astype(np.uint32)
-        assert len(live) >= n_queries // 2 and len(r.hits) == len(live) * len(one_cols) > 8192
-        assert np.array_equal(r.hits["query"], np.repeat(live, len(one_cols))), want_kernel
-        assert np.array_equal(r.hits["column"], np.tile(one_cols, len(live))), want_kernel
-        assert np.array_equal(r.hits["num_match"], np.repeat(nk[live], len(one_cols))), want_kernel
-
-    units = (nbytes + 127) // 128 * 8
-    off = dict(walk=0, count_walk=0, narrow=0, force_segs=0, walk_bands=0)
-    if units <= 32:
-        with ctx.tuning(**dict(off, narrow=1)):
-            check(g.search(b, 1.0), "and_narrow_kernel<")
-            if units > 8:
-                check(g.search(b, 0.5), "count_narrow_kernel<")
-    for vec in (1, 2, 4):
-        with ctx.tuning(**dict(off, and_vec=vec)):
-            check(g.search(b, 1.0), "and_kernel<%d," % vec)
-    with ctx.tuning(**dict(off, force_segs=3)):
-        check(g.search(b, 1.0), "and_kernel<")
-        assert g.search(b, 1.0).search_kernel.endswith("+segments")
-        check(g.search(b, 0.5), "count_kernel<")
-    with ctx.tuning(**off):
-        check(g.search(b, 0.5), "count_kernel<")
-    if units >= 64:
-        # early exit, every tile handed over to the refine launch after its first eight rows: one reservation per cluster
-        # (= per query and KiB-step), by the emit launch; and with lists of three places: most tiles walk on by themselves
-        for knobs in (dict(refine_max_groups=16, refine_min_rows=1, refine_seg_rows=8), dict(refine_max_groups=16, refine_min_rows=1, refine_list_cap=3)):
-            with ctx.tuning(**dict(off, count_screen_min_tiles=1, **knobs)):
-                check(g.search(b, 1.0, ka.SEARCH_EARLY_EXIT), "and_screen_kernel<")
-                check(g.search(b, 0.5, ka.SEARCH_EARLY_EXIT), "count_screen_kernel<")
-    for waves in (0, 37):
-        with ctx.tuning(**dict(off, count_walk=1, count_walk_min_rows=1, count_walk_waves=waves)):
-            check(g.search(b, 0.5), "count_walk_kernel<")
-        if units >= 2 * 64:
-            with ctx.tuning(**dict(off, walk=4, walk_min_rows=1, walk_max_kib=64, walk_waves=waves)):
-                check(g.search(b, 1.0), "and_walk_kernel<")
-            if units <= 16 * 64:
-                with ctx.tuning(**dict(off, walk=4, walk_min_rows=1, walk_waves=waves, walk_bands=3, walk_bands_min_gib=0)):
-                    check(g.search(b, 1.0), "and_band_walk_kernel<")
-    b.close()
-    g.close()
+    seen = drive_every_kernel_form(ka, ctx, n_cols, np.arange(n_cols) % 7 != 3, n_queries, seed=n_cols)
+    assert {"and_kernel<1,", "and_kernel<2,", "and_kernel<4,", "and_kernel<", "count_kernel<", "count_walk_kernel<"} <= set(seen)
 
 
 @pytest.mark.parametrize("n_cols,num_hash,density", [(8192, 1, 0.25), (20000, 2, 0.5), (100000, 1, 0.25), (131073, 3, 0.7)])
