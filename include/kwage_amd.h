@@ -225,8 +225,9 @@ int kwage_group_insert_bloom_files(kwage_group *g, const char *const *paths, uin
  * kwage_group_read_rows.  Their bits are cleared in every row (the host folds the list into distinct (32-bit word, mask)
  * pairs, one thread per (row, pair)), their valid bits are cleared and the column count drops.  Columns may repeat within
  * a call; groups of either kind, finalized or not.  The space is NOT reused: the span and the numbers of all other
- * columns stay, and a later insert continues at the tail.  KWAGE_ERR_ARG, nothing changed, for a column at or beyond
- * the span or one that is (already) a pad column; KWAGE_ERR_STATE while a search is pending.  Synchronous. */
+ * columns stay, and a later insert continues at the tail (kwage_group_save_db writes the surviving columns densely; a
+ * load of that file gives the space back).  KWAGE_ERR_ARG, nothing changed, for a column at or beyond the span or one
+ * that is (already) a pad column; KWAGE_ERR_STATE while a search is pending.  Synchronous. */
 int kwage_group_retire_columns(kwage_group *g, const uint64_t *columns, uint64_t n);
 
 /* ------------------------------------------------------------------------------------
@@ -617,6 +618,43 @@ int kwage_bloom_counter_finish(kwage_bloom_counter *bc, float false_positive_pro
  * the reference's merge_db.cpp:268-820 (get_bit/set_bit per bit there; shift-and-OR on the device
  * here), without its file naming / size policy.  The reference `kwage` reads the result. */
 int kwage_repack_db(kwage_ctx *ctx, const char *out_path, const char *const *in_paths, uint32_t n);
+
+/* Save, no counterpart in the reference: `n` columns of the group's resident matrix, in the order listed, written as ONE
+ * raw `.db` file (compression 0) -- file blocks, live inserts at bit granularity, what is left around retired columns.
+ * The columns are gathered and packed densely on the device; the file is byte for byte what kwage_build_db writes from
+ * the same Bloom filters and metadata in the same order, so a save followed by a load is also the defragmentation that
+ * kwage_group_retire_columns lacks.
+ *   - cols[i].column is a global column of the group and becomes column i of the file.  Its FilterInfo record is copied
+ *     verbatim from column source_column of the `.db` / `.dbz` file source_db (as kwage_repack_db copies records; each
+ *     distinct file is opened once), or, when source_db is NULL, serialized from *info as kwage_make_bloom serializes it;
+ *   - staging_bytes: the size of one chunk of output rows in pinned host memory (two such blocks, used alternately: a
+ *     chunk's CRC32 and file write run on a host thread beside the next chunk's kernel and copy); 0 means 64 MiB, and any
+ *     value works, down to one row per chunk;
+ *   - the file is written under a temporary name beside out_path and renamed at the end: a failure on the device or on
+ *     disk leaves no partial file and an existing out_path as it was; out_path may name one of the source_db files;
+ *   - the group, its valid mask and its span are not changed; before and after kwage_group_finalize;
+ *   - stats may be NULL.
+ * Errors, all found before out_path is touched: KWAGE_ERR_ARG for a NULL argument, n == 0, a sparse group (its matrix
+ * holds only some rows), a column at or beyond the span, a pad or retired column, a column listed twice, an entry with
+ * neither source_db nor info, a source_column beyond its file; KWAGE_ERR_STATE while a search is pending on the context;
+ * KWAGE_ERR_IO / KWAGE_ERR_FORMAT for an unreadable or damaged source of metadata.
+ * Synchronous; runs on the context's first stream. */
+typedef struct {
+	uint64_t column;                 /* global column of the group                                              */
+	const char *source_db;           /* copy this column's FilterInfo record verbatim from column source_column */
+	uint32_t source_column;          /*   of this .db / .dbz file ...                                           */
+	const kwage_sample_info *info;   /* ... or, when source_db is NULL, serialize this (as kwage_make_bloom does) */
+} kwage_save_column;
+
+typedef struct {
+	uint64_t db_bytes;               /* size of the file written            */
+	uint64_t runs;                   /* runs the column list folded into    */
+	uint32_t chunks;                 /* staged chunks of rows               */
+	float extract_kernel_ms;         /* sum over chunks, HIP events         */
+} kwage_save_stats;
+
+int kwage_group_save_db(kwage_group *g, const char *out_path, const kwage_save_column *cols, uint32_t n,
+                        uint64_t staging_bytes, kwage_save_stats *stats);
 
 /* ------------------------------------------------------------------------------------
  * Host-side helpers that mirror the reference's host code for this path (no device needed).

@@ -18,6 +18,7 @@
 #include <zlib.h>
 
 #include "bloom_files.hpp"
+#include "db_writer.hpp"
 #include "host.hpp"
 #include "internal.h"
 #include "transpose_tile.hpp"
@@ -120,22 +121,6 @@ __global__ void pack_columns_kernel(uint32_t *dst, uint64_t dst_stride_words, ui
 	}
 }
 
-// crc32 of a large buffer continued from `crc`: parts in parallel, stitched with crc32_combine
-// (the result is identical to one sequential crc32_z call).
-uint32_t crc32_parallel(uint32_t crc, const unsigned char *buf, uint64_t len)
-{
-	const unsigned nthread = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
-	if(len < (8u << 20) || nthread == 1){ return (uint32_t)crc32_z(crc, buf, len); }
-	const uint64_t part = (len + nthread - 1)/nthread;
-	std::vector<uint32_t> pc(nthread, 0);
-	std::vector<uint64_t> pl(nthread, 0);
-	for(unsigned t = 0; t < nthread; ++t){ pl[t] = ((uint64_t)t*part < len) ? std::min(part, len - (uint64_t)t*part) : 0; }
-	run_parts(nthread, [&](unsigned t) { if(pl[t]){ pc[t] = (uint32_t)crc32_z(crc32_z(0L, Z_NULL, 0), buf + (uint64_t)t*part, pl[t]); } });
-	uint64_t out = crc;
-	for(unsigned t = 0; t < nthread && pl[t]; ++t){ out = crc32_combine(out, pc[t], (z_off_t)pl[t]); }
-	return (uint32_t)out;
-}
-
 }  // namespace
 
 // The device context internals this file needs (defined in engine.hip).
@@ -165,17 +150,13 @@ extern "C" int kwage_build_db(kwage_ctx *ctx, const char *out_path, const kwage_
 
 	// header placeholder (rewritten at the end with crc32 + info_start), kwage.h:36-46
 	unsigned char hdr[DB_HEADER_BYTES];
-	auto put32 = [](unsigned char *p, uint32_t v) { for(int i = 0; i < 4; ++i){ p[i] = (unsigned char)(v >> (8*i)); } };
-	auto put64 = [](unsigned char *p, uint64_t v) { for(int i = 0; i < 8; ++i){ p[i] = (unsigned char)(v >> (8*i)); } };
-	memset(hdr, 0, sizeof(hdr));
-	put32(hdr, KWAGE_MAGIC_NUMBER); put32(hdr + 4, 2 /* CURRENT_DBFILE_VERSION */);
-	put32(hdr + 12, params->kmer_len); put32(hdr + 16, params->num_hash); put32(hdr + 20, params->log_2_filter_len);
-	put32(hdr + 24, n);   // hash_func stays 0 and compression NO_COMPRESSION, as build_db.cpp:189-199 leaves them
+	db_header_placeholder(hdr, *params, n);
 	bool ok = fwrite(hdr, 1, sizeof(hdr), fout) == sizeof(hdr);
 
 	// ---- transpose, chunk by chunk --------------------------------------------------------------
 	// chunk rows: bounded so that the input (n x rows/8) and the output (rows x slice) both stay <= 256 MiB (the output is
-	// double-buffered: a chunk's CRC32 and file write run on a host thread beside the next chunk's gather, copies and kernel)
+	// double-buffered: a chunk's CRC32 and file write run on a host thread beside the next chunk's gather, copies and kernel
+	// -- db_writer.hpp write_db_body)
 	uint64_t chunk_rows = filter_len;
 	while(chunk_rows > 1024 && (chunk_rows/8*n > (256ull << 20) || chunk_rows*slice_size > (256ull << 20))){ chunk_rows /= 2; }
 	// Filters lie `in_stride` apart in the device's input block, and a lane's 32 loads go to 32 consecutive filters at the
@@ -185,13 +166,10 @@ extern "C" int kwage_build_db(kwage_ctx *ctx, const char *out_path, const kwage_
 	uint64_t in_stride = (chunk_bytes + 255)/256*256;
 	if((in_stride/256) % 2 == 0){ in_stride += 256; }
 	if(const char *v = getenv("KWAGE_BUILD_PAD")){ in_stride = (chunk_bytes + 3)/4*4 + (uint64_t)std::max<long long>(atoll(v), 0)/4*4; }      // (never below the chunk itself)
-	void *d_in = nullptr, *d_out = nullptr, *h_in = nullptr, *h_out[2] = {nullptr, nullptr};
+	void *d_in = nullptr, *d_out = nullptr, *h_in = nullptr;
 	hipError_t e = hipMalloc(&d_in, in_stride*n);
 	if(e == hipSuccess){ e = hipMalloc(&d_out, chunk_rows*slice_size); }
 	if(e == hipSuccess){ e = hipHostMalloc(&h_in, in_stride*n, hipHostMallocDefault); }
-	for(int k = 0; k < 2; ++k){ if(e == hipSuccess){ e = hipHostMalloc(&h_out[k], chunk_rows*slice_size, hipHostMallocDefault); } }
-	std::thread writer;                 // CRC32 + fwrite of the previous chunk
-	bool writer_ok = true;
 	uint32_t n_chunk = 0;
 	uint32_t db_crc = 0;            // output_header.crc32 starts at 0 (build_db.cpp:192,307)
 	double t_kernel_ms = 0;
@@ -200,11 +178,7 @@ extern "C" int kwage_build_db(kwage_ctx *ctx, const char *out_path, const kwage_
 	const int tile_shape = []() { const char *v = getenv("KWAGE_BUILD_TILE"); return v ? atoi(v) : 0; }();
 	// (a resident grid walking the tiles with the next tile requested before the current one is written out measured 10 %
 	// SLOWER than one workgroup per tile -- profiles/r04_builder_transpose.txt -- and went in round 5)
-	hipEvent_t ev0 = nullptr, ev1 = nullptr;
-	if(e == hipSuccess){ e = hipEventCreate(&ev0); }
-	if(e == hipSuccess){ e = hipEventCreate(&ev1); }
-	for(uint64_t r0 = 0; r0 < filter_len && ok && e == hipSuccess; r0 += chunk_rows){
-		const uint64_t nr = std::min(chunk_rows, filter_len - r0);
+	auto transpose_chunk = [&](uint64_t r0, uint64_t nr, hipEvent_t ev0, hipEvent_t ev1) -> hipError_t {
 		const uint64_t nb = (nr + 7)/8;
 		{	// this chunk of every filter into the pinned block (host threads: one memcpy per filter, 2048 of up to 256 KB)
 			const unsigned nthread = (uint64_t)n*nb < (8u << 20) ? 1u : std::max(1u, std::min(8u, std::thread::hardware_concurrency()));
@@ -212,8 +186,8 @@ extern "C" int kwage_build_db(kwage_ctx *ctx, const char *out_path, const kwage_
 				for(uint32_t i = t; i < n; i += nthread){ memcpy((char*)h_in + (uint64_t)i*in_stride, files[i].map + files[i].bits_off + r0/8, nb); }
 			});
 		}
-		e = hipMemcpyAsync(d_in, h_in, in_stride*n, hipMemcpyHostToDevice, stream);
-		if(e != hipSuccess){ break; }
+		hipError_t ce = hipMemcpyAsync(d_in, h_in, in_stride*n, hipMemcpyHostToDevice, stream);
+		if(ce != hipSuccess){ return ce; }
 		(void)hipEventRecord(ev0, stream);
 		auto launch = [&](auto tile_tag) {
 			using T = decltype(tile_tag);
@@ -229,52 +203,25 @@ extern "C" int kwage_build_db(kwage_ctx *ctx, const char *out_path, const kwage_
 		default: launch(TransposeTile<16, 8>()); break;
 		}
 		(void)hipEventRecord(ev1, stream);
-		e = hipGetLastError();
-		unsigned char *hb = (unsigned char*)h_out[n_chunk++ & 1];      // (its previous user, two chunks ago, was joined below)
-		if(e == hipSuccess){ e = hipMemcpyAsync(hb, d_out, nr*slice_size, hipMemcpyDeviceToHost, stream); }
-		if(e == hipSuccess){ e = hipStreamSynchronize(stream); }
-		if(e != hipSuccess){ break; }
-		float ms = 0;
-		(void)hipEventElapsedTime(&ms, ev0, ev1);
-		t_kernel_ms += ms;
-		if(writer.joinable()){ writer.join(); }
-		ok = writer_ok;
-		if(!ok){ break; }
-		auto write_chunk = [&db_crc, &writer_ok, fout, hb, bytes = nr*slice_size]() {        // (chunks are written in order: one writer at a time)
-			db_crc = crc32_parallel(db_crc, hb, bytes);
-			writer_ok = fwrite(hb, 1, bytes, fout) == bytes;
-		};
-		try{ writer = std::thread(write_chunk); }
-		catch(...){ write_chunk(); }          // no thread to be had: this chunk is written here (no exception leaves this function)
-	}
-	if(writer.joinable()){ writer.join(); }
-	ok = ok && writer_ok;
+		return hipGetLastError();
+	};
+	if(e == hipSuccess){ e = write_db_body(fout, stream, filter_len, chunk_rows, slice_size, d_out, transpose_chunk, &db_crc, &ok, &t_kernel_ms, &n_chunk); }
 	if(d_in){ (void)hipFree(d_in); }
 	if(d_out){ (void)hipFree(d_out); }
 	if(h_in){ (void)hipHostFree(h_in); }
-	for(int k = 0; k < 2; ++k){ if(h_out[k]){ (void)hipHostFree(h_out[k]); } }
-	if(ev0){ (void)hipEventDestroy(ev0); }
-	if(ev1){ (void)hipEventDestroy(ev1); }
 	if(e != hipSuccess){ fclose(fout); cleanup(); return fail(KWAGE_ERR_DEVICE, "kwage_build_db: %s", hipGetErrorString(e)); }
 
 	// ---- metadata index + records (build_db.cpp:371-416), then the final header (:421-427) -------
 	const uint64_t info_start = DB_HEADER_BYTES + filter_len*slice_size;
 	std::vector<unsigned char> recs;
-	std::vector<uint64_t> loc(n);
-	uint64_t pos = info_start + 8ull*n;
+	std::vector<uint64_t> rec_len(n);
 	for(uint32_t i = 0; i < n; ++i){
-		loc[i] = pos;
 		const size_t before = recs.size();
 		pack_filter_info(files[i].info, recs);
-		pos += recs.size() - before;
+		rec_len[i] = recs.size() - before;
 	}
-	std::vector<unsigned char> locb(8ull*n);
-	for(uint32_t i = 0; i < n; ++i){ put64(locb.data() + 8ull*i, loc[i]); }
-	ok = ok && fwrite(locb.data(), 1, locb.size(), fout) == locb.size();
-	ok = ok && (recs.empty() || fwrite(recs.data(), 1, recs.size(), fout) == recs.size());
-	put32(hdr + 8, db_crc);
-	put64(hdr + 36, info_start);
-	ok = ok && fseek(fout, 0, SEEK_SET) == 0 && fwrite(hdr, 1, sizeof(hdr), fout) == sizeof(hdr);
+	uint64_t pos = 0;
+	ok = write_db_tail(fout, hdr, db_crc, info_start, rec_len, recs, &pos) && ok;
 	ok = (fclose(fout) == 0) && ok;
 	cleanup();
 	if(!ok){ return fail(KWAGE_ERR_IO, "build_db: Error writing database file %s", out_path); }

@@ -7,6 +7,12 @@
 //   kwage_dbtool decompress <in.dbz> <out.db>                       container -> raw (host)
 //   kwage_dbtool build <out.db> <k> <log2 len> <num hash> <f.bloom>...   .bloom files -> .db   (device bit transpose)
 //   kwage_dbtool repack <out.db> <in.db>...                         same-parameter files -> one wide file (device)
+//   kwage_dbtool append <out.db> <in.db> <x.bloom>...               in.db loaded into a group, the filters inserted live behind it
+//                                                                   (kwage_group_insert_bloom_files), everything saved as one
+//                                                                   file (kwage_group_save_db): what `build` makes of all the
+//                                                                   `.bloom` files, without the ones in.db was built from
+//   kwage_dbtool drop <out.db> <in.db> <run accession>...           in.db without the listed samples; exit code 1 when one of
+//                                                                   them is not in the file
 //   kwage_dbtool mkbloom <out.bloom> <accession> <k> <log2 len|0> <num hash|0> <seq file> [p]
 //                                                                   exact k-mer set of a FASTA/FASTQ -> .bloom; 0 0 = pick the
 //                                                                   parameters with optimal_bloom_param(p, default 0.25)
@@ -19,6 +25,8 @@
 #include <cstring>
 #include <string>
 #include <vector>
+
+#include <unistd.h>
 
 #include "kwage_amd.h"
 
@@ -35,9 +43,87 @@ static int usage()
 		"       kwage_dbtool compress <in.db> <out.dbz> [threads] | decompress <in.dbz> <out.db>\n"
 		"       kwage_dbtool build <out.db> <k> <log2 len> <num hash> <f.bloom>...\n"
 		"       kwage_dbtool repack <out.db> <in.db>...\n"
+		"       kwage_dbtool append <out.db> <in.db> <x.bloom>...\n"
+		"       kwage_dbtool drop <out.db> <in.db> <run accession>...\n"
 		"       kwage_dbtool mkbloom <out.bloom> <accession> <k> <log2 len|0> <num hash|0> <seq file> [p]\n"
 		"       kwage_dbtool countbloom <out.bloom> <accession> <k> <min count> <seq file>... [-p p] [-l min log2] [-L max log2]\n");
 	return 2;
+}
+
+// in.db loaded into a fresh group with room for `extra` more columns behind it (on the next 16-byte boundary of the row).
+static int load_db(kwage_ctx *ctx, const char *in_db, uint64_t extra, kwage_db_header *h, kwage_group **g)
+{
+	if(kwage_db_read_header(in_db, h)){ return die("read header"); }
+	const kwage_params p = {h->kmer_len, h->num_hash, h->log_2_filter_len, h->hash_func};
+	const uint64_t file_bytes = ((uint64_t)h->num_filter + 7)/8;
+	if(kwage_group_create(ctx, &p, extra ? (file_bytes + 15)/16*16*8 + extra : file_bytes*8, g)){ return die("create group"); }
+	uint64_t first = 0;
+	uint32_t nf = 0;
+	if(kwage_group_add_db_file(*g, in_db, &first, &nf)){ kwage_group_destroy(*g); *g = NULL; return die("load"); }
+	return 0;
+}
+
+static int save_columns(kwage_group *g, const char *out_db, const std::vector<kwage_save_column> &cols)
+{
+	kwage_save_stats st;
+	if(cols.empty() || cols.size() > 0xFFFFFFFFull){ fprintf(stderr, "kwage_dbtool: save: no column is left to write\n"); return 1; }
+	if(kwage_group_save_db(g, out_db, cols.data(), (uint32_t)cols.size(), 0, &st)){ return die("save"); }
+	fprintf(stderr, "wrote %s: %zu columns, %llu bytes, %llu runs, extract kernel %.3f ms\n", out_db, cols.size(), (unsigned long long)st.db_bytes,
+	        (unsigned long long)st.runs, st.extract_kernel_ms);
+	return 0;
+}
+
+static int append_blooms(kwage_ctx *ctx, const char *out_db, const char *in_db, const char *const *blooms, uint32_t n)
+{
+	kwage_db_header h;
+	kwage_group *g = NULL;
+	int rc = load_db(ctx, in_db, n, &h, &g);
+	if(rc){ return rc; }
+	uint64_t first = 0;
+	if(kwage_group_insert_bloom_files(g, blooms, n, 0, &first, NULL)){ kwage_group_destroy(g); return die("insert"); }
+	// the new columns' FilterInfo records are kwage_build_db's own: a side file of the new filters is built for them and
+	// removed again (a `.bloom` file's record reaches the save verbatim through a `.db` file only)
+	const std::string side = std::string(out_db) + ".records." + std::to_string((long long)getpid());
+	const kwage_params p = {h.kmer_len, h.num_hash, h.log_2_filter_len, h.hash_func};
+	if(kwage_build_db(ctx, side.c_str(), &p, blooms, n, NULL)){ kwage_group_destroy(g); (void)remove(side.c_str()); return die("build"); }
+	std::vector<kwage_save_column> cols;
+	for(uint32_t j = 0; j < h.num_filter; ++j){ cols.push_back(kwage_save_column{j, in_db, j, NULL}); }
+	for(uint32_t j = 0; j < n; ++j){ cols.push_back(kwage_save_column{first + j, side.c_str(), j, NULL}); }
+	rc = save_columns(g, out_db, cols);
+	(void)remove(side.c_str());
+	kwage_group_destroy(g);
+	return rc;
+}
+
+static int drop_samples(kwage_ctx *ctx, const char *out_db, const char *in_db, char **accessions, int n)
+{
+	kwage_dbinfo *d = NULL;
+	if(kwage_dbinfo_open(in_db, &d)){ return die("read metadata"); }
+	std::vector<std::string> have(kwage_dbinfo_num_filter(d));
+	char buf[64];
+	for(uint32_t j = 0; j < have.size(); ++j){
+		if(kwage_dbinfo_csv_string(d, j, buf, sizeof(buf))){ kwage_dbinfo_close(d); return die("read FilterInfo"); }
+		have[j] = buf;
+	}
+	kwage_dbinfo_close(d);
+	for(int i = 0; i < n; ++i){
+		bool found = false;
+		for(const std::string &a : have){ found = found || a == accessions[i]; }
+		if(!found){ fprintf(stderr, "kwage_dbtool: drop: %s holds no sample with run accession %s\n", in_db, accessions[i]); return 1; }
+	}
+	kwage_db_header h;
+	kwage_group *g = NULL;
+	int rc = load_db(ctx, in_db, 0, &h, &g);
+	if(rc){ return rc; }
+	std::vector<kwage_save_column> cols;
+	for(uint32_t j = 0; j < have.size(); ++j){
+		bool gone = false;
+		for(int i = 0; i < n; ++i){ gone = gone || have[j] == accessions[i]; }
+		if(!gone){ cols.push_back(kwage_save_column{j, in_db, j, NULL}); }
+	}
+	rc = save_columns(g, out_db, cols);
+	kwage_group_destroy(g);
+	return rc;
 }
 
 int main(int argc, char **argv)
@@ -72,7 +158,7 @@ int main(int argc, char **argv)
 	}
 
 	// the remaining commands run on the device
-	if(cmd != "build" && cmd != "repack" && cmd != "mkbloom" && cmd != "countbloom"){ return usage(); }
+	if(cmd != "build" && cmd != "repack" && cmd != "append" && cmd != "drop" && cmd != "mkbloom" && cmd != "countbloom"){ return usage(); }
 	kwage_ctx *ctx = NULL;
 	const char *dev = getenv("KWAGE_DEVICE");
 	if(kwage_init(dev ? atoi(dev) : 0, &ctx)){ return die("init"); }
@@ -87,6 +173,12 @@ int main(int argc, char **argv)
 	else if(cmd == "repack" && argc >= 4){
 		rc = kwage_repack_db(ctx, argv[2], argv + 3, (uint32_t)(argc - 3));
 		if(rc){ rc = die("repack"); }
+	}
+	else if(cmd == "append" && argc >= 5){
+		rc = append_blooms(ctx, argv[2], argv[3], argv + 4, (uint32_t)(argc - 4));
+	}
+	else if(cmd == "drop" && argc >= 5){
+		rc = drop_samples(ctx, argv[2], argv[3], argv + 4, argc - 4);
 	}
 	else if(cmd == "mkbloom" && argc >= 8){
 		kwage_seqfile *sf = NULL;

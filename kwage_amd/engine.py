@@ -220,6 +220,35 @@ class Group:
         self._real = real
         self._column_bits = None
 
+    def save_db(self, path: str, columns: Sequence[int], sources: Sequence, staging_bytes: int = 0) -> dict:
+        """Write the listed columns, in list order, as one raw `.db` file (kwage_group_save_db): gathered and packed on the
+        device, byte for byte what kwage_build_db writes from the same filters.  sources[i] says where column i's
+        FilterInfo record comes from: (db_path, column) copies it from that file, a dict of kwage_sample_info fields
+        (at least run_accession) serializes it.  Returns the call's stats."""
+        n = len(columns)
+        assert len(sources) == n, (len(sources), n)
+        cols = (native.SaveColumn * max(n, 1))()
+        keep = []                                    # what the entries point to, alive until the call returns
+        for i, (c, src) in enumerate(zip(columns, sources)):
+            cols[i].column = int(c)
+            if isinstance(src, dict):
+                si = native.SampleInfo()
+                for k, v in src.items():
+                    if k in ("attribute_tags", "attribute_values"):
+                        arr = (C.c_char_p * len(v))(*[s.encode("latin-1") for s in v])
+                        keep.append(arr)
+                        setattr(si, k, arr)
+                    else:
+                        setattr(si, k, v.encode("latin-1") if isinstance(v, str) else v)
+                keep.append(si)
+                cols[i].info = C.pointer(si)
+            elif src is not None:
+                cols[i].source_db = str(src[0]).encode()
+                cols[i].source_column = int(src[1])
+        st = native.SaveStats()
+        check(lib().kwage_group_save_db(self._h, path.encode(), cols, n, staging_bytes, C.byref(st)))
+        return {"db_bytes": st.db_bytes, "runs": st.runs, "chunks": st.chunks, "extract_kernel_ms": st.extract_kernel_ms}
+
     def set_bits(self, rows: np.ndarray, columns: np.ndarray) -> None:
         rows = np.ascontiguousarray(rows, dtype=np.uint32)
         columns = np.ascontiguousarray(columns, dtype=np.uint64)
@@ -889,6 +918,27 @@ class FileDatabase(Database):
         else:
             self._retired.add((gi, col))
         return gi, col
+
+    def save(self, out_dir: str, max_columns: int = 2048) -> List[str]:
+        """Write the database as it stands -- live samples included, retired ones left out -- as `.db` files under out_dir
+        (Group.save_db): group by group, every sample of _samples() in report order (file samples, then live samples), in
+        files of at most max_columns columns (the reference's file width).  A file sample keeps the record of its own
+        file; a live sample gets its recorded run accession and no other field.  FileDatabase(ctx, [out_dir]) afterwards
+        answers as this database does.  Returns the files written."""
+        import os
+        assert max_columns >= 1
+        os.makedirs(out_dir, exist_ok=True)
+        written = []
+        for gi, g in enumerate(self.groups):
+            mine = [(col, {"run_accession": path.accessions[c]} if isinstance(path, _LiveBlock) else (path, c))
+                    for sgi, col, path, c in self._samples() if sgi == gi]
+            p = g.params
+            for part, at in enumerate(range(0, len(mine), max_columns)):
+                piece = mine[at:at + max_columns]
+                out = os.path.join(out_dir, "k%d_L%d_h%d_f%d_%04d.db" % (p.kmer_len, p.log_2_filter_len, p.num_hash, p.hash_func, part))
+                g.save_db(out, [c for c, _ in piece], [s for _, s in piece])
+                written.append(out)
+        return written
 
     def _accession(self, path: str, column: int) -> str:
         if isinstance(path, _LiveBlock):

@@ -74,6 +74,14 @@ class BuildStats(C.Structure):
     _fields_ = [("bits_transposed", C.c_uint64), ("transpose_kernel_ms", C.c_float), ("db_bytes", C.c_uint64)]
 
 
+class SaveColumn(C.Structure):
+    """kwage_save_column (filled in below SampleInfo, which it points to)"""
+
+
+class SaveStats(C.Structure):
+    _fields_ = [("db_bytes", C.c_uint64), ("runs", C.c_uint64), ("chunks", C.c_uint32), ("extract_kernel_ms", C.c_float)]
+
+
 class BloomCounterStats(C.Structure):
     _fields_ = [("num_valid_kmer", C.c_uint64), ("num_bp", C.c_uint64), ("positions", C.c_uint64),
                 ("occurrences_committed", C.c_uint64), ("chunks", C.c_uint64), ("rounds", C.c_uint64),
@@ -89,6 +97,9 @@ class SampleInfo(C.Structure):
                [("attribute_tags", C.POINTER(C.c_char_p)), ("attribute_values", C.POINTER(C.c_char_p)),
                 ("num_attributes", C.c_uint32), ("number_of_spots", C.c_uint64), ("number_of_bases", C.c_uint64),
                 ("day", C.c_uint32), ("month", C.c_uint32), ("year", C.c_uint32)]
+
+
+SaveColumn._fields_ = [("column", C.c_uint64), ("source_db", C.c_char_p), ("source_column", C.c_uint32), ("info", C.POINTER(SampleInfo))]
 
 
 class DbHeader(C.Structure):
@@ -187,6 +198,7 @@ _SIGNATURES = [
     ("kwage_bloom_counter_read_valid_bits", C.c_int, [_P, C.c_uint32, C.c_uint64, C.c_uint64, _P]),
     ("kwage_bloom_counter_finish", C.c_int, [_P, C.c_float, C.c_uint32, C.POINTER(SampleInfo), C.c_char_p, C.POINTER(Params), C.POINTER(C.c_int)]),
     ("kwage_repack_db", C.c_int, [_P, C.c_char_p, C.POINTER(C.c_char_p), C.c_uint32]),
+    ("kwage_group_save_db", C.c_int, [_P, C.c_char_p, C.POINTER(SaveColumn), C.c_uint32, C.c_uint64, C.POINTER(SaveStats)]),
     ("kwage_db_read_header", C.c_int, [C.c_char_p, C.POINTER(DbHeader)]),
     ("kwage_db_read_slices", C.c_int, [C.c_char_p, C.POINTER(C.c_uint32), C.c_uint64, C.c_void_p]),
     ("kwage_db_compress", C.c_int, [C.c_char_p, C.c_char_p, C.c_uint32]),
