@@ -224,11 +224,45 @@ int kwage_group_insert_bloom_files(kwage_group *g, const char *const *paths, uin
  * 0 in score, presence and kwage_group_column_bits output, refused by kwage_filterset_from_columns, zeros in
  * kwage_group_read_rows.  Their bits are cleared in every row (the host folds the list into distinct (32-bit word, mask)
  * pairs, one thread per (row, pair)), their valid bits are cleared and the column count drops.  Columns may repeat within
- * a call; groups of either kind, finalized or not.  The space is NOT reused: the span and the numbers of all other
- * columns stay, and a later insert continues at the tail (kwage_group_save_db writes the surviving columns densely; a
- * load of that file gives the space back).  KWAGE_ERR_ARG, nothing changed, for a column at or beyond the span or one
+ * a call; groups of either kind, finalized or not.  Retire itself does NOT reuse the space: the span and the numbers of
+ * all other columns stay, and a later insert continues at the tail.  kwage_group_compact gives the space back in place
+ * (kwage_group_save_db writes the surviving columns densely; a load of that file does it too).  KWAGE_ERR_ARG, nothing changed, for a column at or beyond the span or one
  * that is (already) a pad column; KWAGE_ERR_STATE while a search is pending.  Synchronous. */
 int kwage_group_retire_columns(kwage_group *g, const uint64_t *columns, uint64_t n);
+
+/* Compaction, no counterpart in the reference: the gaps that retired columns and the alignment pads of file blocks leave
+ * are closed IN PLACE, one pass over the matrix in HBM -- what a save followed by a load also does, without the file and
+ * without a second copy of the matrix.  The m valid columns keep their ascending order and become columns 0 .. m - 1;
+ * afterwards the matrix is bit for bit what ONE call of the host form of the live insert, given the survivors at
+ * column 0, would have made.
+ *   - the span becomes 8 * ceil(m / 8), row_bytes = ceil(m / 8); bits m .. span - 1 of every row are zero, and so is
+ *     everything from there up to the old span; the valid mask holds exactly bits [0, m); the column count, the row
+ *     stride, the allocation and the row count stay; the tail is open at column m, so the next live insert continues
+ *     there at bit granularity and the freed capacity is available at once;
+ *   - before and after the finalize call; a finalized group stays finalized and re-samples its bit densities as the live
+ *     insert does.  Every search submitted after the call returns sees the new column numbers;
+ *   - new_column (may be NULL) receives, for every column c below the OLD span, the column's new number -- the number of
+ *     valid columns below c -- or KWAGE_NO_COLUMN for a pad or retired column; capacity is the number of entries the
+ *     array holds;
+ *   - a destination column never lies above its source, so a row is rewritten left to right in segments of 16-byte
+ *     units: a segment's units are all made in registers before any of them is stored (a workgroup barrier between the
+ *     two), one 16-byte store per unit, no atomics.  Units wholly below the first pad or retired column are not touched;
+ *   - m == 0 is allowed: the span becomes 0 and no kernel is launched.  A group with nothing to close (every column
+ *     below the tail valid) launches nothing and returns the identity map;
+ *   - flags: KWAGE_SEARCH_TIMING fills stats->kernel_ms with the HIP-event duration of the kernel; other bits are
+ *     ignored.  stats may be NULL.
+ * Errors, all found before a byte is written -- the matrix, valid mask and span are then as before: KWAGE_ERR_ARG for a
+ * NULL group, a sparse group, a non-NULL new_column with capacity below the old span; KWAGE_ERR_STATE while a search is
+ * pending on the context.  Synchronous; runs on the context's first stream. */
+#define KWAGE_NO_COLUMN 0xFFFFFFFFFFFFFFFFull
+typedef struct {
+	uint64_t span_before, span_after;   /* kwage_group_column_span before / after            */
+	uint64_t columns;                   /* valid columns m (unchanged by the call)           */
+	uint64_t runs;                      /* stretches of consecutive surviving columns        */
+	uint64_t first_unit, units;         /* 16-byte units of a row rewritten: [first_unit, first_unit + units) */
+	float    kernel_ms;                 /* with KWAGE_SEARCH_TIMING in flags, else 0         */
+} kwage_compact_stats;
+int kwage_group_compact(kwage_group *g, uint32_t flags, uint64_t *new_column, uint64_t capacity, kwage_compact_stats *stats);
 
 /* ------------------------------------------------------------------------------------
  * Query batch: raw sequences (any case, any characters -- exactly what the reference hands to
@@ -622,8 +656,8 @@ int kwage_repack_db(kwage_ctx *ctx, const char *out_path, const char *const *in_
 /* Save, no counterpart in the reference: `n` columns of the group's resident matrix, in the order listed, written as ONE
  * raw `.db` file (compression 0) -- file blocks, live inserts at bit granularity, what is left around retired columns.
  * The columns are gathered and packed densely on the device; the file is byte for byte what kwage_build_db writes from
- * the same Bloom filters and metadata in the same order, so a save followed by a load is also the defragmentation that
- * kwage_group_retire_columns lacks.
+ * the same Bloom filters and metadata in the same order, so a save followed by a load also defragments what
+ * kwage_group_retire_columns leaves (kwage_group_compact does that in place, without the file).
  *   - cols[i].column is a global column of the group and becomes column i of the file.  Its FilterInfo record is copied
  *     verbatim from column source_column of the `.db` / `.dbz` file source_db (as kwage_repack_db copies records; each
  *     distinct file is opened once), or, when source_db is NULL, serialized from *info as kwage_make_bloom serializes it;

@@ -1,6 +1,6 @@
 // kwage_amd/csrc/save.hip -- save: chosen columns of a group's RESIDENT matrix written as one raw `.db` file, packed
-// densely on the device -- the missing half of the live insert (insert.hip), and with a load behind it the
-// defragmentation that retire lacks.  No counterpart in the reference, whose only writer is build_db().
+// densely on the device -- the missing half of the live insert (insert.hip); with a load behind it it also defragments
+// what retire leaves (compact.hip does that in place).  No counterpart in the reference, whose only writer is build_db().
 //
 //   which columns, in what order   save_plan.hpp plan_save: the list folded into runs of consecutive columns
 //   who writes what                save_kernels.hpp extract_columns_kernel: one thread per 16 bytes of an output row

@@ -204,7 +204,7 @@ class Group:
         return self._inserted(first.value, n)
 
     def retire_columns(self, cols: Sequence[int]) -> None:
-        """Withdraw columns (kwage_group_retire_columns): pad columns from here on; their space is not reused."""
+        """Withdraw columns (kwage_group_retire_columns): pad columns from here on; compact() gives their space back."""
         cols = np.ascontiguousarray(cols, dtype=np.uint64)
         check(lib().kwage_group_retire_columns(self._h, cols.ctypes.data if cols.size else None, cols.size))
         gone = sorted(set(int(c) for c in cols.tolist()))
@@ -219,6 +219,20 @@ class Group:
                 real.append((at, first + nf - at))
         self._real = real
         self._column_bits = None
+
+    def compact(self, timing: bool = False) -> Tuple[np.ndarray, dict]:
+        """Close the gaps that retired columns and alignment pads leave, in place (kwage_group_compact): the m valid
+        columns become columns 0 .. m - 1 in their order, the span shrinks and the next insert continues at column m.
+        Returns (new_column, stats): int64 [old column_span], a column's new number or -1 for a pad or retired column,
+        and the call's stats."""
+        span = self.column_span
+        new = np.empty(max(span, 1), dtype=np.uint64)
+        st = native.CompactStats()
+        check(lib().kwage_group_compact(self._h, SEARCH_TIMING if timing else 0, new.ctypes.data_as(C.POINTER(C.c_uint64)), span, C.byref(st)))
+        new = new[:span].view(np.int64)              # (KWAGE_NO_COLUMN is -1 as int64)
+        self._real = [(0, int(st.columns))] if st.columns else []
+        self._column_bits = None
+        return new, {f: getattr(st, f) for f, _ in native.CompactStats._fields_}
 
     def save_db(self, path: str, columns: Sequence[int], sources: Sequence, staging_bytes: int = 0) -> dict:
         """Write the listed columns, in list order, as one raw `.db` file (kwage_group_save_db): gathered and packed on the
@@ -835,7 +849,7 @@ class FileDatabase(Database):
     grouped by (kmer_len, num_hash, log_2_filter_len, hash_func), each group one HBM matrix; hits are
     mapped back to (file, column) and carry the sample's run accession.  With headroom > 0 every group has room for
     that many more columns: add_sample() makes new samples searchable in the resident groups (live insert),
-    retire_sample() withdraws one."""
+    retire_sample() withdraws one, compact() gives the withdrawn samples' columns back to add_sample()."""
 
     def __init__(self, ctx: Context, paths: Sequence[str], headroom: int = 0):
         import os
@@ -866,7 +880,7 @@ class FileDatabase(Database):
                 span = (span + 15) // 16 * 16 + (nf + 7) // 8
             # (live inserts start on the 16-byte boundary behind the files)
             g = Group(ctx, k, nh, lg, span * 8 if headroom <= 0 else (span + 15) // 16 * 16 * 8 + headroom, hf)
-            firsts = [(first, nf, f) for (first, nf), (f, _) in zip(g.add_db_files([f for f, _ in members]), members)]
+            firsts = [(first, nf, f, 0) for (first, nf), (f, _) in zip(g.add_db_files([f for f, _ in members]), members)]
             g.finalize()
             groups.append(g)
             self._layout.append(firsts)
@@ -876,16 +890,21 @@ class FileDatabase(Database):
         self._retired = set()                         # (group index, column) of the FILE columns retire_sample() withdrew
 
     def _blocks(self):
-        """(group index, first column, columns, path) of every block in report order: the files in file order, then the
-        live blocks group by group."""
-        where = {path: (gi, first, nf) for gi, layout in enumerate(self._layout) for first, nf, path in layout if not isinstance(path, _LiveBlock)}
-        out = [where[f] + (f,) for f in self.files]
-        out.extend((gi, first, nf, path) for gi, layout in enumerate(self._layout) for first, nf, path in layout if isinstance(path, _LiveBlock))
+        """(group index, first column, columns, path, first column within the file) of every piece of the layout in report
+        order: the files in file order (a file that compact() cut around a retired column: its pieces in column order),
+        then the live blocks group by group.  A layout entry is (first column, columns, path, first column within the file)."""
+        where = {}
+        for gi, layout in enumerate(self._layout):
+            for first, nf, path, f0 in layout:
+                if not isinstance(path, _LiveBlock):
+                    where.setdefault(path, []).append((gi, first, nf, path, f0))
+        out = [piece for f in self.files for piece in where.get(f, [])]
+        out.extend((gi, first, nf, path, f0) for gi, layout in enumerate(self._layout) for first, nf, path, f0 in layout if isinstance(path, _LiveBlock))
         return out
 
     def _samples(self):
         """(group index, column in the group, path, column in the block) of every sample in report order."""
-        return [(gi, first + c, path, c) for gi, first, nf, path in self._blocks() for c in range(nf) if (gi, first + c) not in self._retired]
+        return [(gi, first + c, path, f0 + c) for gi, first, nf, path, f0 in self._blocks() for c in range(nf) if (gi, first + c) not in self._retired]
 
     def add_sample(self, accession: str, seqs: Sequence[bytes | str], group: int = 0) -> Tuple[int, int]:
         """Make one new sample searchable at once: its Bloom filter is built on the device from `seqs` at the parameters of
@@ -901,7 +920,7 @@ class FileDatabase(Database):
         finally:
             b.close()
         col = g.insert_filters(bits)
-        self._layout[group].append((col, 1, _LiveBlock([accession])))
+        self._layout[group].append((col, 1, _LiveBlock([accession]), 0))
         return group, col
 
     def retire_sample(self, accession: str) -> Tuple[int, int]:
@@ -918,6 +937,28 @@ class FileDatabase(Database):
         else:
             self._retired.add((gi, col))
         return gi, col
+
+    def compact(self) -> List[dict]:
+        """Close the gaps that retired samples and the files' alignment pads leave, in every resident group
+        (Group.compact): the freed columns are add_sample()'s again.  Columns are renumbered -- the layout follows, a file
+        with a retired column in the middle becoming two pieces -- and every method answers as before, with the new
+        numbers where it shows columns of a group.  Returns each group's stats."""
+        stats = []
+        for gi, g in enumerate(self.groups):
+            new, st = g.compact()
+            layout = []
+            for first, nf, path, f0 in self._layout[gi]:
+                kept = [c for c in range(nf) if new[first + c] >= 0]
+                for i, c in enumerate(kept):
+                    if i and kept[i - 1] == c - 1:
+                        at, n, p, f = layout[-1]
+                        layout[-1] = (at, n + 1, p, f)
+                    else:
+                        layout.append((int(new[first + c]), 1, path, f0 + c))
+            self._layout[gi] = layout
+            self._retired = {(g2, c) for g2, c in self._retired if g2 != gi}
+            stats.append(st)
+        return stats
 
     def save(self, out_dir: str, max_columns: int = 2048) -> List[str]:
         """Write the database as it stands -- live samples included, retired ones left out -- as `.db` files under out_dir
@@ -963,8 +1004,8 @@ class FileDatabase(Database):
                 starts = [f[0] for f in layout]
                 for q, c, m in r.hits.tolist():
                     i = bisect.bisect_right(starts, c) - 1
-                    first, _, path = layout[i]
-                    out.append(DatabaseHit(q, path, c - first, self._accession(path, c - first), m, int(r.num_query_kmer[q])))
+                    first, _, path, f0 = layout[i]
+                    out.append(DatabaseHit(q, path, c - first + f0, self._accession(path, c - first + f0), m, int(r.num_query_kmer[q])))
         finally:
             b.close()
         out.sort(key=lambda h: (h.query, -h.num_kmers_found, h.path, h.column))
@@ -984,8 +1025,8 @@ class FileDatabase(Database):
                 starts = [f[0] for f in layout]
                 for q, c, m in r.hits.tolist():
                     i = bisect.bisect_right(starts, c) - 1
-                    first, _, path = layout[i]
-                    per_query.setdefault(q, []).append((m, path, c - first, int(r.num_query_kmer[q]), gi, c))
+                    first, _, path, f0 = layout[i]
+                    per_query.setdefault(q, []).append((m, path, c - first + f0, int(r.num_query_kmer[q]), gi, c))
         finally:
             b.close()
         out: List[DatabaseHit] = []
@@ -1050,8 +1091,8 @@ class FileDatabase(Database):
                 for g2, c, sh, fb, cb, jv in lst:
                     layout = self._layout[g2]
                     at = bisect.bisect_right([f[0] for f in layout], c) - 1
-                    first, _, path = layout[at]
-                    rec.append((self._accession(path, c - first), path, c - first, sh, fb, cb, jv))
+                    first, _, path, f0 = layout[at]
+                    rec.append((self._accession(path, c - first + f0), path, c - first + f0, sh, fb, cb, jv))
                 result[i] = (accessions[i], rec)
         return result
 

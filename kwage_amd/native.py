@@ -82,6 +82,14 @@ class SaveStats(C.Structure):
     _fields_ = [("db_bytes", C.c_uint64), ("runs", C.c_uint64), ("chunks", C.c_uint32), ("extract_kernel_ms", C.c_float)]
 
 
+class CompactStats(C.Structure):
+    _fields_ = [("span_before", C.c_uint64), ("span_after", C.c_uint64), ("columns", C.c_uint64), ("runs", C.c_uint64),
+                ("first_unit", C.c_uint64), ("units", C.c_uint64), ("kernel_ms", C.c_float)]
+
+
+NO_COLUMN = 0xFFFFFFFFFFFFFFFF                        # KWAGE_NO_COLUMN
+
+
 class BloomCounterStats(C.Structure):
     _fields_ = [("num_valid_kmer", C.c_uint64), ("num_bp", C.c_uint64), ("positions", C.c_uint64),
                 ("occurrences_committed", C.c_uint64), ("chunks", C.c_uint64), ("rounds", C.c_uint64),
@@ -147,6 +155,7 @@ _SIGNATURES = [
     ("kwage_group_insert_filters_device", C.c_int, [_P, _P, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_float)]),
     ("kwage_group_insert_bloom_files", C.c_int, [_P, C.POINTER(C.c_char_p), C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_float)]),
     ("kwage_group_retire_columns", C.c_int, [_P, _P, C.c_uint64]),
+    ("kwage_group_compact", C.c_int, [_P, C.c_uint32, C.POINTER(C.c_uint64), C.c_uint64, C.POINTER(CompactStats)]),
     ("kwage_batch_create", C.c_int, [_P, C.c_char_p, _P, C.c_uint32, C.POINTER(_P)]),
     ("kwage_batch_destroy", None, [_P]),
     ("kwage_batch_num_queries", C.c_uint32, [_P]),
