@@ -25,6 +25,7 @@
 #include "host.hpp"
 #include "engine_state.hpp"
 #include "kernels.hpp"
+#include "search_plan.hpp"
 
 using namespace kwage;
 
@@ -347,36 +348,6 @@ int launch_remap_rows(const kwage_group *g, uint32_t n_queries, const KmerLayout
 	return KWAGE_OK;
 }
 
-// counter planes for counts up to `max_count`: the smallest instantiated size whose bits hold it
-uint32_t planes_for(uint64_t max_count)
-{
-	uint32_t bits = 1;
-	while(bits < 32 && (max_count >> bits) != 0){ ++bits; }
-	return (bits <= 7) ? 7 : (bits <= 10) ? 10 : (bits <= 14) ? 14 : (bits <= 20) ? 20 : 32;
-}
-
-// How many segments to cut each query's k-mer list into: none while the launch already has
-// enough waves to fill the chip; otherwise enough to reach ~TARGET_TILES waves (about 8 per CU, ~2x the bytes in flight that cover HBM latency), but never segments
-// shorter than MIN_SEG_KMERS k-mers.  The force_segs knob forces a count (tests).
-void choose_segments(SearchArgs &a, uint64_t max_kmers, uint64_t max_segs, int64_t force_segs)
-{
-	static const uint64_t TARGET_TILES = 2048, MIN_SEG_KMERS = 64;
-	const uint64_t MAX_SEGS = max_segs;
-	a.segs = 1;
-	a.seg_kmers = (uint32_t)std::max<uint64_t>(max_kmers, 1);
-	uint64_t want = 1;
-	if(force_segs > 0){ want = (uint64_t)force_segs; }
-	else{
-		const uint64_t tiles = (uint64_t)a.n_queries*a.chunks;
-		if(tiles >= TARGET_TILES || max_kmers < 2*MIN_SEG_KMERS){ return; }
-		want = std::min<uint64_t>((TARGET_TILES + tiles - 1)/tiles, max_kmers/MIN_SEG_KMERS);
-	}
-	want = std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint64_t>(want, MAX_SEGS), std::max<uint64_t>(max_kmers, 1)));
-	if(want <= 1){ return; }
-	a.seg_kmers = (uint32_t)((max_kmers + want - 1)/want);
-	a.segs = (uint32_t)((max_kmers + a.seg_kmers - 1)/a.seg_kmers);
-}
-
 int fail_missing_rows(unsigned long long missing)
 {
 	return fail(KWAGE_ERR_STATE, "%llu row indices of this batch are not among the rows of the sparse group (it was created for other queries)", missing);
@@ -387,26 +358,25 @@ uint32_t tile_chunks(const kwage_group *g) { return ((uint32_t)(g->stride/16) + 
 int plan_tiles(const kwage_group *g, uint64_t max_count, uint32_t slice, uint64_t max_combine_wgs, TilePlan *plan)
 {
 	static const uint64_t SLAB_BYTES_PER_SLICE = 1ull << 30;       // partial counters of one slice of the queries (segmented form)
-	SearchArgs a;
-	memset(&a, 0, sizeof(a));
-	a.chunks = tile_chunks(g);
+	const uint32_t chunks = tile_chunks(g);
 	uint32_t planes = 0, seg_planes = 0;
+	Segments sg = {0, 0};
 	if(slice){
+		int rc;
 		planes = planes_for(max_count);
-		a.n_queries = slice;
-		choose_segments(a, max_count, 1024, g->ctx->tune.force_segs);
-		seg_planes = (a.segs > 1) ? planes_for(a.seg_kmers) : planes;
-		if(a.segs > 1){      // keep the slab of partial counters bounded: fewer queries per slice
-			const uint64_t slab_per_q = (uint64_t)a.segs*seg_planes*g->stride;
+		sg = choose_segments(slice, chunks, max_count, 1024, g->ctx->tune.force_segs);
+		seg_planes = (sg.segs > 1) ? planes_for(sg.seg_kmers) : planes;
+		if(sg.segs > 1){      // keep the slab of partial counters bounded: fewer queries per slice
+			const uint64_t slab_per_q = (uint64_t)sg.segs*seg_planes*g->stride;
 			slice = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(slice, SLAB_BYTES_PER_SLICE/slab_per_q));
 			if(max_combine_wgs){
-				if(a.chunks > max_combine_wgs){ return fail(KWAGE_ERR_ARG, "batch too large for one launch"); }
-				slice = (uint32_t)std::min<uint64_t>(slice, max_combine_wgs/a.chunks);
+				if(chunks > max_combine_wgs){ return fail_launch_size(); }
+				slice = (uint32_t)std::min<uint64_t>(slice, max_combine_wgs/chunks);
 			}
 		}
-		if((uint64_t)slice*a.segs*a.chunks/4 + 1 > 0x7FFFFFFFull){ return fail(KWAGE_ERR_ARG, "batch too large for one launch"); }
+		if((rc = check_launch_size(slice, sg.segs, chunks))){ return rc; }
 	}
-	*plan = TilePlan{(uint32_t)(g->stride/16), a.chunks, planes, seg_planes, a.segs, a.seg_kmers, slice};
+	*plan = TilePlan{(uint32_t)(g->stride/16), chunks, planes, seg_planes, sg.segs, sg.seg_kmers, slice};
 	return KWAGE_OK;
 }
 
@@ -475,164 +445,100 @@ struct StageEvents { hipEvent_t start = nullptr, stop = nullptr; };
 #define KW_GATHER_LAUNCH(ge, first, last, kernel, grid, block, lds, stream, ...) \
 	hipExtLaunchKernelGGL(kernel, grid, block, (uint32_t)(lds), stream, (first) ? (ge).start : nullptr, (last) ? (ge).stop : nullptr, 0u, __VA_ARGS__)
 
-static const uint32_t WALK_MIN_ROWS_PER_WAVE = 64;   // and_walk_kernel: below this share per wave the tiled kernel is used
-static const uint32_t WALK_WAVES_PER_CU = 8;         // 2 workgroups: 2048 waves measured 1-2 % faster than 4096 (half the cut pairs)
+static_assert(sizeof(RefineUnit) == REFINE_UNIT_BYTES, "search_plan.hpp sizes the unit list with it");
 
-uint32_t search_blocks(const SearchArgs &a)
+// f(integral_constant<int, V>) for the V of the list that v equals -- the last one where none does --: the template
+// integers of a plan to the instantiations that exist (by_planes and by_nh of engine_state.hpp, for any list)
+template <int V, int... REST, typename F>
+void by_int(int v, F &&f)
 {
-	const uint64_t tiles = (uint64_t)a.n_queries*a.segs*a.chunks;
-	return (uint32_t)((tiles + 3)/4);
-}
-
-// Launch shape of a persistent kernel that wants `want_waves` waves.  A chip-filling launch (8 waves per CU) uses ONE
-// workgroup of 8 waves per CU -- a dynamic-LDS pad of more than half a CU's LDS keeps a second workgroup off --, so
-// that every CU runs exactly 8 waves; smaller launches use workgroups of four waves wherever the dispatcher puts them.
-struct WalkShape { uint32_t wgs, wg_waves; size_t lds; };
-static const size_t WALK_PAD_LDS = 100*1024;
-
-WalkShape walk_shape(const Tuning &tn, uint64_t want_waves, uint64_t ncu)
-{
-	WalkShape w;
-	const bool pinned = tn.walk_one_wg_per_cu && want_waves == ncu*WALK_WG_WAVES;
-	w.wg_waves = pinned ? (uint32_t)WALK_WG_WAVES : 4u;
-	w.wgs = (uint32_t)((want_waves + w.wg_waves - 1)/w.wg_waves);
-	w.lds = pinned ? WALK_PAD_LDS : 0;
-	return w;
-}
-
-// Shape of the tiled AND kernel: VEC 16-byte vectors per lane (by row width; knob and_vec), and -- the WIDE shape only -- a
-// dynamic-LDS pad that caps the waves per CU.  Eight rows in flight and nontemporal loads always.
-struct AndCfg { int vec, lds_bytes; };
-
-// `wide`: rows beyond the walk form's range searched without early exit by a launch that fills the chip (C3, C4 and their
-// column shares): four vectors per lane, eight rows in flight, and a dynamic-LDS pad that keeps 8 waves per CU resident
-// -- 32 KiB in flight per wave, 256 KiB per CU.  As for the persistent kernels, the memory system prefers few deep
-// streams to many: against the default shape (32 waves per CU, 16 KiB each) +1.4 % on C3 and on the C4 share in one
-// process (12 waves per CU +0.4 %, 16 and 20 the same as the default, 4 waves per CU -20 %; profiles/r04_tune_and_wide_rows.txt).
-AndCfg and_config(const Tuning &t, uint32_t units_per_row, bool wide = false)
-{
-	AndCfg c;
-	if(wide && t.and_vec == 0){ c.vec = 4; c.lds_bytes = 80*1024; return c; }
-	c.vec = (t.and_vec == 1 || t.and_vec == 2 || t.and_vec == 4) ? (int)t.and_vec : ((units_per_row >= 4*WAVE) ? 2 : 1);
-	c.lds_bytes = 0;
-	return c;
-}
-
-template <int VEC>
-void launch_and(const SearchArgs &a, hipStream_t s, const AndCfg &c, const StageEvents &ge)
-{
-	const uint64_t tiles = (uint64_t)a.n_queries*a.segs*a.chunks;
-	const uint32_t bw = SEARCH_THREADS/WAVE;
-	const dim3 grid((uint32_t)((tiles + bw - 1)/bw)), block(SEARCH_THREADS);
-	if(c.lds_bytes > 48*1024){
-		(void)hipFuncSetAttribute((const void*)and_kernel<VEC, false>, hipFuncAttributeMaxDynamicSharedMemorySize, c.lds_bytes);
-	}
-	if(a.segs > 1){
-		KW_GATHER_LAUNCH(ge, true, false, (and_kernel<VEC, true>), grid, block, 0, s, a);      // (and_combine_kernel ends the stage)
-	}
+	if constexpr(sizeof...(REST) == 0){ f(std::integral_constant<int, V>()); }
 	else{
-		KW_GATHER_LAUNCH(ge, true, true, (and_kernel<VEC, false>), grid, block, c.lds_bytes, s, a);
+		if(v == V){ f(std::integral_constant<int, V>()); }
+		else{ by_int<REST...>(v, f); }
 	}
 }
+// KiB-steps of a column tile of the walk form
+template <typename F>
+void by_ch(uint32_t ch, F &&f) { by_int<1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16>((int)ch, f); }
 
-void launch_and_v(const SearchArgs &a, hipStream_t s, const AndCfg &c, const StageEvents &ge)
+// the tiled AND kernel over the plan's tiles
+void launch_and(const SearchPlan &p, const SearchArgs &a, hipStream_t s, const StageEvents &ge)
 {
-	if(c.vec == 1){ launch_and<1>(a, s, c, ge); }
-	else if(c.vec == 2){ launch_and<2>(a, s, c, ge); }
-	else{ launch_and<4>(a, s, c, ge); }
-}
-
-// count_kernel with `planes` counter planes over the launch's tiles
-void launch_count(uint32_t planes, const SearchArgs &a, hipStream_t s, const StageEvents &ge)
-{
-	by_shape(planes, a.num_hash, [&](auto P, auto NH) {
-		constexpr int PLANES = decltype(P)::value, H = decltype(NH)::value;
-		if(a.segs > 1){
-			KW_GATHER_LAUNCH(ge, true, false, (count_kernel<PLANES, H, true>), dim3(search_blocks(a)), dim3(SEARCH_THREADS), 0, s, a);      // (count_combine_kernel ends the stage)
+	const dim3 grid(p.wgs), block(p.wg_waves*WAVE);
+	by_int<1, 2, 4>(p.vec, [&](auto V) {
+		constexpr int VEC = decltype(V)::value;
+		if(p.lds > 48*1024){
+			(void)hipFuncSetAttribute((const void*)and_kernel<VEC, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);
+		}
+		if(p.segs > 1){
+			KW_GATHER_LAUNCH(ge, true, false, (and_kernel<VEC, true>), grid, block, 0, s, a);      // (and_combine_kernel ends the stage)
 		}
 		else{
-			KW_GATHER_LAUNCH(ge, true, true, (count_kernel<PLANES, H, false>), dim3(search_blocks(a)), dim3(SEARCH_THREADS), 0, s, a);
+			KW_GATHER_LAUNCH(ge, true, true, (and_kernel<VEC, false>), grid, block, p.lds, s, a);
 		}
 	});
 }
 
-// count_narrow_kernel and count_screen_kernel exist for 7, 10 and 14 planes only (their callers have seen planes <= 14)
-template <typename F>
-void by_planes_to_14(uint32_t planes, F &&f)
+// count_kernel with the plan's segment planes over its tiles
+void launch_count(const SearchPlan &p, const SearchArgs &a, hipStream_t s, const StageEvents &ge)
 {
-	if(planes == 7){ f(std::integral_constant<int, 7>()); }
-	else if(planes == 10){ f(std::integral_constant<int, 10>()); }
-	else{ f(std::integral_constant<int, 14>()); }
-}
-
-// G queries per wave
-template <int G>
-void launch_count_narrow(uint32_t planes, const SearchArgs &a, hipStream_t s, const StageEvents &ge)
-{
-	const uint64_t waves = ((uint64_t)a.n_queries + G - 1)/G;
-	const dim3 grid((uint32_t)((waves + 3)/4)), block(SEARCH_THREADS);
-	by_planes_to_14(planes, [&](auto P) {
-		by_nh(a.num_hash, [&](auto NH) {
-			KW_GATHER_LAUNCH(ge, true, true, (count_narrow_kernel<decltype(P)::value, decltype(NH)::value, G>), grid, block, 0, s, a);
-		});
+	const dim3 grid(p.wgs), block(p.wg_waves*WAVE);
+	by_shape(p.seg_planes, a.num_hash, [&](auto P, auto NH) {
+		constexpr int PLANES = decltype(P)::value, H = decltype(NH)::value;
+		if(p.segs > 1){
+			KW_GATHER_LAUNCH(ge, true, false, (count_kernel<PLANES, H, true>), grid, block, 0, s, a);      // (count_combine_kernel ends the stage)
+		}
+		else{
+			KW_GATHER_LAUNCH(ge, true, true, (count_kernel<PLANES, H, false>), grid, block, 0, s, a);
+		}
 	});
 }
+
+// count_narrow_kernel and count_screen_kernel exist for 7, 10 and 14 planes only (the plan gives them planes <= 14)
+template <typename F>
+void by_planes_to_14(uint32_t planes, F &&f) { by_int<7, 10, 14>((int)planes, f); }
 
 template <bool TRUNC>
-void launch_count_walk(uint32_t planes, const SearchArgs &a, const CountWalkArgs &wa, const RefineArgs &ra, const WalkShape &w, hipStream_t s, const StageEvents &ge)
+void launch_count_walk(const SearchPlan &p, uint32_t planes, const SearchArgs &a, const CountWalkArgs &wa, const RefineArgs &ra, hipStream_t s, const StageEvents &ge)
 {
 	by_shape(planes, a.num_hash, [&](auto P, auto NH) {
-		// (the truncated form counts a query of up to 127 k-mers with ten planes: the caller sizes slab and lists for that)
+		// (the truncated form counts a query of up to 127 k-mers with ten planes: the plan sizes slab and lists for that)
 		constexpr int PLANES = (TRUNC && decltype(P)::value == 7) ? 10 : decltype(P)::value;
 		const auto kernel = count_walk_kernel<PLANES, decltype(NH)::value, TRUNC>;
-		if(w.lds > 48*1024){ (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)w.lds); }
+		if(p.lds > 48*1024){ (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds); }
 		// (TRUNC: the refine and emit launches end the stage)
-		KW_GATHER_LAUNCH(ge, true, !TRUNC, kernel, dim3(w.wgs), dim3(w.wg_waves*WAVE), w.lds, s, a, wa, ra, a.rows, a.pos_off, a.nkmer, a.qthr);
+		KW_GATHER_LAUNCH(ge, true, !TRUNC, kernel, dim3(p.wgs), dim3(p.wg_waves*WAVE), p.lds, s, a, wa, ra, a.rows, a.pos_off, a.nkmer, a.qthr);
 	});
 }
 
-struct RefineSetup { RefineArgs ra; uint32_t refine_wgs, emit_wgs; };
-
 // The refine and emit launches of the count path's early-exit forms (count_screen_kernel, the truncated count walk).
-// Units of 14 planes (up == 14) pair count_refine_kernel<NH, 14> with count_refine_emit_kernel<P, 14>, which exists for
-// P >= 14 only: any other pairing would read the slab with a stride it was not written with.  Checked before the first
-// launch of the stage.
-int check_refine_units(uint32_t planes, int up)
-{
-	if(up == 14 && planes < 14){ return fail(KWAGE_ERR_STATE, "count refine: 14-plane units with %u counter planes", planes); }
-	return KWAGE_OK;
-}
-
-void launch_count_refine_and_emit(uint32_t planes, int up, const SearchArgs &a, const RefineSetup &rs, hipStream_t gs, const StageEvents &ge)
+void launch_count_refine_and_emit(uint32_t planes, const SearchPlan &p, const SearchArgs &a, const RefineArgs &ra, hipStream_t gs, const StageEvents &ge)
 {
 	const dim3 block(SEARCH_THREADS);
 	by_nh(a.num_hash, [&](auto NH) {
-		constexpr int H = decltype(NH)::value;
-		if(up == 7){ KW_GATHER_LAUNCH(ge, false, false, (count_refine_kernel<H, 7>), dim3(rs.refine_wgs), block, 0, gs, a, rs.ra); }
-		else{ KW_GATHER_LAUNCH(ge, false, false, (count_refine_kernel<H, 14>), dim3(rs.refine_wgs), block, 0, gs, a, rs.ra); }
+		by_int<7, 14>(p.up, [&](auto UP) {
+			KW_GATHER_LAUNCH(ge, false, false, (count_refine_kernel<decltype(NH)::value, decltype(UP)::value>), dim3(p.refine.refine_wgs), block, 0, gs, a, ra);
+		});
 	});
 	by_planes(planes, [&](auto P) {
-		constexpr int PLANES = decltype(P)::value, UP14 = (PLANES >= 14) ? 14 : 7;      // (<P, 14> exists for P >= 14 only: check_refine_units)
-		if(up == 7){ KW_GATHER_LAUNCH(ge, false, true, (count_refine_emit_kernel<PLANES, 7>), dim3(rs.emit_wgs), block, 0, gs, a, rs.ra); }
-		else{ KW_GATHER_LAUNCH(ge, false, true, (count_refine_emit_kernel<PLANES, UP14>), dim3(rs.emit_wgs), block, 0, gs, a, rs.ra); }
+		constexpr int PLANES = decltype(P)::value, UP14 = (PLANES >= 14) ? 14 : 7;      // (<P, 14> exists for P >= 14 only: the plan's check_refine_units)
+		if(p.up == 7){ KW_GATHER_LAUNCH(ge, false, true, (count_refine_emit_kernel<PLANES, 7>), dim3(p.refine.emit_wgs), block, 0, gs, a, ra); }
+		else{ KW_GATHER_LAUNCH(ge, false, true, (count_refine_emit_kernel<PLANES, UP14>), dim3(p.refine.emit_wgs), block, 0, gs, a, ra); }
 	});
 }
 
-int launch_count_combine(uint32_t planes, const SearchArgs &a, uint32_t seg_planes, hipStream_t s, const StageEvents &ge)
+int launch_count_combine(const SearchPlan &p, const SearchArgs &a, hipStream_t s, const StageEvents &ge)
 {
-	return by_planes(planes, [&](auto P) -> int {
+	return by_planes(p.planes, [&](auto P) -> int {
 		constexpr int PLANES = decltype(P)::value;
 		constexpr size_t lds = (size_t)(COMBINE_WAVES/2)*PLANES*WAVE*16;
 		int rc;
 		if((rc = allow_dynamic_lds(count_combine_kernel<PLANES>, lds))){ return rc; }
-		KW_GATHER_LAUNCH(ge, false, true, (count_combine_kernel<PLANES>), dim3((a.units_per_row + WAVE - 1)/WAVE, a.n_queries), dim3(COMBINE_WAVES*WAVE), lds, s, a, seg_planes);
+		KW_GATHER_LAUNCH(ge, false, true, (count_combine_kernel<PLANES>), dim3(p.combine_wgs, a.n_queries), dim3(COMBINE_WAVES*WAVE), lds, s, a, p.seg_planes);
 		return KWAGE_OK;
 	});
 }
-
-// The segment limit of a launch of this search: its combine kernels index queries with gridDim.y, so no segments above
-// 65535 queries.
-uint64_t max_segments(const SearchArgs &a, uint64_t max_segs) { return (a.n_queries > 65535) ? 1 : max_segs; }
 
 // A scratch buffer the kernels leave all zero: cleared when it is (re)allocated, never per search.
 int reserve_zeroed(DevBuf &buf, uint64_t bytes, hipStream_t s)
@@ -644,51 +550,24 @@ int reserve_zeroed(DevBuf &buf, uint64_t bytes, hipStream_t s)
 	return KWAGE_OK;
 }
 
-// The lists of the early-exit form "screen, then refine" (kernels.hpp and_screen_kernel), sized from the batch: room for
-// eight handed-over 128-byte groups per query (three planted columns per query is what the synthetic workloads hold; a
-// tile that finds the lists full walks on by itself) and for the units of as many items of average length.  Half of
-// every list is static -- its places dealt out to the `screen_waves` waves of the screen launch beforehand, taken without an
-// atomic --, the rest is reserved in chunks through three counters, zeroed on the gather stream before every stage.
-// `item_bytes`: mask (t = 1: 128) or counters (t < 1: planes x 128) per item; `unit_bytes`: partial counters per unit
-// (t < 1 only).
-int refine_setup(Slot *sl, const Tuning &tn, const SearchArgs &a, uint64_t total_rows, uint64_t max_rows, uint32_t max_seg, uint64_t item_bytes, uint64_t unit_bytes,
-                 uint64_t tiles, uint64_t screen_waves, uint64_t ncu, hipStream_t gs, RefineSetup *out,
-                 uint64_t exact_clusters = 0, uint64_t exact_items = 0, uint64_t exact_units = 0)
+// The lists of the early-exit forms as the plan sized them (search_plan.hpp refine_plan): reserved, the three counters
+// zeroed on the gather stream, the kernels' argument record filled.
+int refine_setup(Slot *sl, const RefinePlan &r, hipStream_t gs, RefineArgs *out)
 {
 	int rc;
-	RefineArgs &ra = out->ra;
-	ra.seg_rows = (uint32_t)std::min<int64_t>(std::max<int64_t>(tn.refine_seg_rows, 8), max_seg);
-	ra.seg_rows = (uint32_t)std::max<uint64_t>(ra.seg_rows, (max_rows + 65535)/65536);              // (at most 2^16 units per item; the count path passes its own segment length)
-	ra.min_rows = (uint32_t)std::max<int64_t>(tn.refine_min_rows, 1);
-	ra.max_groups = (uint32_t)std::min<int64_t>(std::max<int64_t>(tn.refine_max_groups, 0), 16);      // (0: nothing is ever handed over)
-	uint64_t items = std::min<uint64_t>(std::max<uint64_t>(8ull*a.n_queries, 1u << 16), 1u << 20);
-	items = std::max<uint64_t>(std::min<uint64_t>(items, (256ull << 20)/item_bytes), 1024);
-	uint64_t units = std::min<uint64_t>(std::max<uint64_t>(32*total_rows/ra.seg_rows, 1u << 18), 1u << 25);       // (32 bytes each: at most 1 GiB)
-	if(unit_bytes){ units = std::max<uint64_t>(std::min<uint64_t>(units, (512ull << 20)/unit_bytes), 4096); }
-	if(tn.refine_list_cap > 0){ items = units = (uint64_t)std::min<int64_t>(tn.refine_list_cap, 1 << 20); }
-	uint64_t clusters = items;
-	// (the truncated count walk names its capacities: a place for every pair and group, units by memory)
-	if(exact_units){ clusters = exact_clusters; items = exact_items; units = exact_units; }
-	if(exact_units && tn.refine_list_cap > 0){ clusters = items = units = (uint64_t)std::min<int64_t>(tn.refine_list_cap, 1 << 20); }       // (tests: full lists)
-	// dynamic chunks: what a wave is likely to need for a few of its tiles (a wave with one or two tiles takes exactly what it needs)
-	const uint64_t tiles_per_wave = (tiles + screen_waves - 1)/std::max<uint64_t>(screen_waves, 1);
-	auto list = [&](uint64_t cap, uint64_t stat_max, uint64_t chunk_max) {
-		RefineList ls;
-		ls.cap = (uint32_t)cap;
-		// (exact capacities: every place is taken exactly when it is needed -- no static parts, no chunks, nothing left unused)
-		ls.stat = (tn.refine_static && !exact_units) ? (uint32_t)std::min<uint64_t>(stat_max, cap/2/std::max<uint64_t>(screen_waves, 1)) : 0u;
-		ls.base = (uint32_t)(ls.stat*screen_waves);
-		ls.chunk = exact_units ? 1u : (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(chunk_max, tiles_per_wave/4));
-		return ls;
-	};
-	ra.lc = list(clusters, 32, 32);
-	ra.li = list(items, 64, 64);
-	ra.lu = list(units, 256, 256);
+	RefineArgs &ra = *out;
+	auto list = [](const ListPlan &l) { return RefineList{l.cap, l.stat, l.base, l.chunk}; };
+	ra.seg_rows = r.seg_rows;
+	ra.min_rows = r.min_rows;
+	ra.max_groups = r.max_groups;
+	ra.lc = list(r.lc);
+	ra.li = list(r.li);
+	ra.lu = list(r.lu);
 	if((rc = sl->ref_counters.reserve(8*sizeof(uint32_t)))){ return rc; }
-	if((rc = sl->ref_clusters.reserve(clusters*sizeof(RefineCluster)))){ return rc; }
-	if((rc = sl->ref_masks.reserve(items*item_bytes))){ return rc; }
-	if((rc = sl->ref_units.reserve(units*sizeof(RefineUnit)))){ return rc; }
-	if(unit_bytes && (rc = sl->ref_slab.reserve(units*unit_bytes))){ return rc; }
+	if((rc = sl->ref_clusters.reserve(r.clusters*sizeof(RefineCluster)))){ return rc; }
+	if((rc = sl->ref_masks.reserve(r.items*r.item_bytes))){ return rc; }
+	if((rc = sl->ref_units.reserve(r.units*sizeof(RefineUnit)))){ return rc; }
+	if(r.unit_bytes && (rc = sl->ref_slab.reserve(r.units*r.unit_bytes))){ return rc; }
 	ra.counters = (uint32_t*)sl->ref_counters.p;
 	ra.clusters = (RefineCluster*)sl->ref_clusters.p;
 	ra.masks = (uint32_t*)sl->ref_masks.p;
@@ -697,10 +576,23 @@ int refine_setup(Slot *sl, const Tuning &tn, const SearchArgs &a, uint64_t total
 	HIP_TRY(hipMemsetAsync(ra.counters, 0, 8*sizeof(uint32_t), gs));
 	sl->ref_base[0] = ra.lc.base; sl->ref_base[1] = ra.li.base; sl->ref_base[2] = ra.lu.base;
 	sl->ref_cap[0] = ra.lc.cap; sl->ref_cap[1] = ra.li.cap; sl->ref_cap[2] = ra.lu.cap;
-	ra.queue_batch = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(16, tiles/(8*std::max<uint64_t>(screen_waves, 1))));
-	ra.check_every = (tn.count_screen_check == 16 || tn.count_screen_check == 32 || tn.count_screen_check == 64) ? (uint32_t)tn.count_screen_check : 8u;
-	out->refine_wgs = (uint32_t)(ncu*8);          // 32 waves per CU, eight units each
-	out->emit_wgs = (uint32_t)(ncu*4);            // 16 waves per CU, four clusters at a time each
+	ra.queue_batch = r.queue_batch;
+	ra.check_every = r.check_every;
+	return KWAGE_OK;
+}
+
+// count_walk_kernel's shares and exchange buffers as the plan sized them (no truncation tables)
+int count_walk_setup(Slot *sl, const SearchPlan &p, hipStream_t gs, CountWalkArgs *wa)
+{
+	int rc;
+	wa->total_slots = p.total_slots;
+	wa->per_wave = p.per_wave;
+	wa->coltiles = p.chunks;
+	if((rc = sl->cwalk_slab.reserve(p.exchange_bytes))){ return rc; }
+	if((rc = reserve_zeroed(sl->cwalk_arrived, p.flags_bytes, gs))){ return rc; }
+	wa->slab = (uint32_t*)sl->cwalk_slab.p;
+	wa->arrived = (uint32_t*)sl->cwalk_arrived.p;
+	wa->slot_off = nullptr; wa->kcut = nullptr;
 	return KWAGE_OK;
 }
 
@@ -712,23 +604,55 @@ uint32_t count_screen_blocks_per_cu(uint32_t planes, uint32_t nh)
 	if(cache[pi][ni] == 0){
 		int nb = 0;
 		hipError_t e = hipErrorUnknown;
-#define KWAGE_OCC_NH(P, N) case N: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, count_screen_kernel<P, N>, SEARCH_THREADS, 0); break;
-#define KWAGE_OCC_P(I, P) case I: switch(ni + 1){ KWAGE_OCC_NH(P, 1) KWAGE_OCC_NH(P, 2) KWAGE_OCC_NH(P, 3) KWAGE_OCC_NH(P, 4) default: KWAGE_OCC_NH(P, 5) } break;
-		switch(pi){ KWAGE_OCC_P(0, 7) KWAGE_OCC_P(1, 10) default: KWAGE_OCC_P(2, 14) }
-#undef KWAGE_OCC_P
-#undef KWAGE_OCC_NH
+		by_planes_to_14(planes, [&](auto P) {
+			by_nh(nh, [&](auto NH) {
+				e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, count_screen_kernel<decltype(P)::value, decltype(NH)::value>, SEARCH_THREADS, 0);
+			});
+		});
 		if(e != hipSuccess || nb <= 0){ (void)hipGetLastError(); nb = 2; }
 		cache[pi][ni] = nb;
 	}
 	return (uint32_t)cache[pi][ni];
 }
 
-// Launch the gather+reduce kernel(s) for the current batch.
+// Launch the gather+reduce kernel(s) for the current batch: search_plan.hpp decides and sizes (plan_search), each case
+// here reserves what the plan sized, fills the form's argument records and launches.
 int launch_search_stage(Slot *sl, kwage_group *g, kwage_batch *b, const KmerLayout *L, float threshold, uint32_t flags,
                         kwage_hit *d_hits, uint64_t cap, unsigned long long *hit_count, hipStream_t gs, const StageEvents &ge)
 {
 	const Tuning &tn = g->ctx->tune;
-	const uint64_t ncu = (uint64_t)std::max(g->ctx->ncu, 1);
+	SearchInputs in;
+	in.ncu = (uint64_t)std::max(g->ctx->ncu, 1);
+	in.stride = g->stride;
+	in.nrows = g->nrows;
+	in.num_hash = g->params.num_hash;
+	in.alloc_bytes = g->alloc_bytes;
+	in.mixes_regions = g->mixes_regions;
+	in.density_max = g->density_max;
+	in.n_queries = b->n;
+	in.total_pos = L->total_pos;
+	in.max_pos = L->max_pos;
+	in.h_pos_off = L->h_pos_off.data();
+	in.threshold = threshold;
+	in.flags = flags;
+	in.count_screen_blocks_per_cu = count_screen_blocks_per_cu;
+	int rc;
+	// (the truncated count walk's tables are planned into the slot's pinned block: the copy to the device reads it there)
+	uint64_t *h_soff = nullptr;
+	uint32_t *h_kcut = nullptr;
+	const bool trunc_tables = search_plan_fills_trunc_tables(tn, in);
+	if(trunc_tables){
+		if((rc = sl->trunc_host.reserve(((uint64_t)b->n + 1)*sizeof(uint64_t) + (uint64_t)b->n*sizeof(uint32_t)))){ return rc; }
+		h_soff = (uint64_t*)sl->trunc_host.p;
+		h_kcut = (uint32_t*)(h_soff + b->n + 1);
+	}
+	SearchPlan p;
+	rc = plan_search(tn, in, h_soff, h_kcut, p);
+	static const bool trunc_debug = getenv("KWAGE_TRUNC_DEBUG") != nullptr;
+	if(trunc_debug && trunc_tables){ fprintf(stderr, "[kwage_amd] truncated count walk: sampled density %.5f, densest column %.5f, per-k-mer match probability planned with %.5f\n", g->density, g->density_max, p.trunc_pm); }
+	if(rc){ return rc; }
+	format_search_name(p, sl->kernel_name, sizeof(sl->kernel_name));
+
 	SearchArgs a;
 	a.db = g->d_bits;
 	a.stride = g->stride;
@@ -739,381 +663,140 @@ int launch_search_stage(Slot *sl, kwage_group *g, kwage_batch *b, const KmerLayo
 	a.nkmer = sl->d_nkmer;
 	a.qthr = sl->d_qthr;
 	a.num_hash = g->params.num_hash;
+	a.chunks = p.chunks;
 	a.n_queries = b->n;
 	a.hits = d_hits;
 	a.cap = cap;
 	a.hit_count = hit_count;
 	a.early_exit = (flags & KWAGE_SEARCH_EARLY_EXIT) ? 1 : 0;
+	a.segs = p.segs;
+	a.seg_kmers = p.seg_kmers;
 	a.partial = nullptr;
 	a.col_base = sl->col_base;
 	a.runs = sl->n_runs ? (unsigned long long*)sl->runs.p : nullptr;
 	a.runs_per_query = sl->runs_per_query;
-	int rc;
+	const dim3 grid(p.wgs), block(p.wg_waves*WAVE);
 
-	if(threshold == 1.0f){
-		// The wide shape of the tiled kernel (and_config) where a launch without early exit fills the chip with 4 KiB tiles: for
-		// rows beyond the walk form's range.  (Within that range the walk form is ahead for every row-list length since its
-		// waves buffer their hit records: a rule that sent batches of short row lists to the wide shape was dropped in round 4,
-		// its knob in round 5; profiles/r04_walk_vs_tiled_wide_grid.txt, r04_walk_hit_cost.txt.)
-		const uint64_t wide_tiles = (uint64_t)a.n_queries*((a.units_per_row + 4*WAVE - 1)/(4*WAVE));
-		const bool wide_ok = tn.and_wide && !(flags & KWAGE_SEARCH_EARLY_EXIT) && wide_tiles >= 8*ncu;
-		const bool wide_rows = wide_ok && a.units_per_row > (uint32_t)std::max<int64_t>(tn.and_wide_min_kib, 1)*WAVE;
-		const AndCfg cfg = and_config(tn, a.units_per_row, wide_rows);
-		a.chunks = (a.units_per_row + WAVE*cfg.vec - 1)/(WAVE*cfg.vec);
-		choose_segments(a, L->max_pos, max_segments(a, 4096), tn.force_segs);
-		if((uint64_t)a.n_queries*a.segs*a.chunks/4 + 1 > 0x7FFFFFFFull){ return fail(KWAGE_ERR_ARG, "batch too large for one launch"); }
-		// narrow rows: several queries per wave (tools/bench_narrow.py)
-		if(tn.narrow && a.segs == 1 && a.units_per_row <= 32 && a.n_queries >= 64){
-			const uint32_t G = (a.units_per_row <= 4) ? 16 : (a.units_per_row <= 8) ? 8 : (a.units_per_row <= 16) ? 4 : 2;
-			const uint64_t waves = ((uint64_t)a.n_queries + G - 1)/G;
-			const dim3 grid((uint32_t)((waves + 3)/4)), block(SEARCH_THREADS);
-			// few waves (10 k queries of 1 kb: ten per CU): sixteen rows in flight per wave instead of eight
-			const int unroll = (waves < ncu*16) ? 16 : 8;
-			snprintf(sl->kernel_name, sizeof(sl->kernel_name), "and_narrow_kernel<%u,%d>", G, unroll);
-#define KWAGE_NARROW_CASE(GG) case GG: \
-				if(unroll == 16){ KW_GATHER_LAUNCH(ge, true, true, (and_narrow_kernel<GG, 16>), grid, block, 0, gs, a); } \
-				else{ KW_GATHER_LAUNCH(ge, true, true, (and_narrow_kernel<GG, 8>), grid, block, 0, gs, a); } break;
-			switch(G){
-				KWAGE_NARROW_CASE(16) KWAGE_NARROW_CASE(8) KWAGE_NARROW_CASE(4)
-				default: KWAGE_NARROW_CASE(2)
-			}
-#undef KWAGE_NARROW_CASE
-			HIP_TRY(hipGetLastError());
-			return KWAGE_OK;
-		}
-		// early exit on rows of a KiB and more: screen, then refine (kernels.hpp and_screen_kernel)
-		if(a.early_exit && tn.ee_refine && a.units_per_row >= WAVE && tn.force_segs <= 0){
-			RefineSetup rs;
-			const int vec = (a.units_per_row >= 4*WAVE) ? 2 : 1;
-			a.segs = 1;
-			a.chunks = (a.units_per_row + WAVE*vec - 1)/(WAVE*vec);
-			const uint64_t tiles = (uint64_t)a.n_queries*a.chunks;
-			// (a persistent grid: tile t goes to wave t mod waves; 20 waves per CU is what the kernel's registers allow)
-			const uint64_t screen_waves = (std::min<uint64_t>(tiles, ncu*(uint64_t)std::max<int64_t>(tn.screen_wpc, 1)) + 3)/4*4;
-			if((rc = refine_setup(sl, tn, a, L->total_pos*a.num_hash, L->max_pos*a.num_hash, 1u << 20, 128, 0, tiles, screen_waves, ncu, gs, &rs))){ return rc; }
-			const int unroll = (tn.refine_unroll == 16) ? 16 : 8;
-			snprintf(sl->kernel_name, sizeof(sl->kernel_name), "and_screen_kernel<%d,8>+refine<%d>", vec, unroll);
-			const dim3 grid((uint32_t)(screen_waves/4)), block(SEARCH_THREADS);
-			if(vec == 2){ KW_GATHER_LAUNCH(ge, true, false, (and_screen_kernel<2, 8>), grid, block, 0, gs, a, rs.ra); }
-			else{ KW_GATHER_LAUNCH(ge, true, false, (and_screen_kernel<1, 8>), grid, block, 0, gs, a, rs.ra); }
-			if(unroll == 16){ KW_GATHER_LAUNCH(ge, false, false, (and_refine_kernel<16>), dim3(rs.refine_wgs), block, 0, gs, a, rs.ra); }
-			else{ KW_GATHER_LAUNCH(ge, false, false, (and_refine_kernel<8>), dim3(rs.refine_wgs), block, 0, gs, a, rs.ra); }
-			KW_GATHER_LAUNCH(ge, false, true, and_refine_emit_kernel, dim3(rs.emit_wgs), block, 0, gs, a, rs.ra);
-			HIP_TRY(hipGetLastError());
-			return KWAGE_OK;
-		}
-		// rows of 3..16 KiB: the walk form (a persistent grid, every wave walks an equal share of the batch's row
-		// list over the whole width of a column tile; kernels.hpp and_walk_kernel).  Worth it once every wave of
-		// the chip gets a few dozen rows; smaller batches stay with the tiled kernel and its row-list segments.
-		const int walk_knob = (int)tn.walk;
-		const uint64_t walk_min_rows = (tn.walk_min_rows >= 0) ? (uint64_t)tn.walk_min_rows : (uint64_t)WALK_MIN_ROWS_PER_WAVE*256*WALK_WAVES_PER_CU;
-		const uint32_t kib = (a.units_per_row + WAVE - 1)/WAVE;
-		// (the kernel handles wider rows as several balanced column tiles -- the walk_max_kib knob raises the limit --
-		// but 125 KB rows measured no gain over the tiled kernel)
-		const uint32_t walk_max_kib = (uint32_t)std::max<int64_t>(tn.walk_max_kib, 0);
-		// (knob walk_tile_kib: narrower column tiles -- with 4, eight rows in flight and no pacing a wave requests 4 KiB of each
-		// of eight rows at once: the tiled kernel's wide shape on the balanced persistent grid)
-		const uint32_t walk_tile = (uint32_t)std::min<int64_t>(std::max<int64_t>(tn.walk_tile_kib, 1), 16);
-		const uint32_t coltiles = (kib + walk_tile - 1)/walk_tile, walk_ch = (kib + coltiles - 1)/coltiles;     // balanced tiles of <= walk_tile KiB
-		// (early exit never comes here: a walking wave covers a column tile's whole width and has nothing to give up --
-		// C2 with early exit measured 1.29 ms through the walk form against 0.64 ms tiled; the screen + refine form above
-		// takes rows of a KiB and more, the tiled kernel below the rest)
-		const bool walk_ee_ok = !a.early_exit;
-		const uint64_t walk_slots = (uint64_t)coltiles*L->total_pos;
-		const uint32_t walk_min_kib = (uint32_t)std::max<int64_t>(tn.walk_min_kib, 1);
-		// rows in flight per wave: 4; 8 for rows of one or two KiB-steps (a group of four such rows is only 4-8 loads: C2's
-		// columns split 8 ways, 1664-byte rows, 0.2626 vs 0.2667 ms)
-		const int walk_unroll = (walk_ch <= 2) ? 8 : 4;
-		if(walk_knob && walk_ee_ok && kib >= walk_min_kib && kib <= walk_max_kib && walk_slots*a.num_hash >= walk_min_rows && walk_slots > 0){
-			// WALK_WAVES_PER_CU waves per CU, all resident at once (__launch_bounds__(256, 4) allows twice as many),
-			// fewer when the batch is small: a wave should have WALK_MIN_ROWS_PER_WAVE rows to walk
-			const uint64_t chip_waves = ncu*WALK_WAVES_PER_CU;
-			const uint64_t want_waves = (tn.walk_waves > 0) ? std::min<uint64_t>((uint64_t)tn.walk_waves, walk_slots)
-				: std::max<uint64_t>(1, std::min<uint64_t>(chip_waves, walk_slots*a.num_hash/WALK_MIN_ROWS_PER_WAVE));
-			const WalkShape shape = walk_shape(tn, want_waves, ncu);
-			const uint32_t wgs = shape.wgs;
-			const uint64_t waves = (uint64_t)wgs*shape.wg_waves;
-			// Band after band (and_band_walk_kernel): matrices large enough to span several regions of the device's memory,
-			// one column tile, a slot of 16 KiB per query affordable.  (With early exit the tiled kernel is the default anyway.)
-			const uint64_t band_items = L->total_pos*a.num_hash;
-			// (a matrix of at least walk_bands_min_gib either way: the probe's "mixes regions" on a 14 GB matrix of 1.6 KB rows --
-			// C2's columns split 8 ways -- sent that shape through the band form at 2.8x the walk form's time)
-			const bool big_enough = g->alloc_bytes >= ((uint64_t)std::max<int64_t>(tn.walk_bands_min_gib, 0) << 30);
-			const uint32_t bands = !big_enough ? 0u : (tn.walk_bands < 0) ? (g->mixes_regions ? 3u : 0u) : (uint32_t)std::min<int64_t>(tn.walk_bands, BAND_MAX);
-			// (rows of one or two KiB-steps stay with the plain walk form: the band kernels are instantiated for 3..16 KiB-steps)
-			if(bands >= 2 && coltiles == 1 && walk_ch >= 3 &&
-			   (uint64_t)a.n_queries*16*1024 <= (256ull << 20) && band_items < 0x7FFFFFFFull){
-				BandArgs ba;
-				ba.bands = bands;
-				ba.rows_per_band = (uint32_t)((g->nrows + bands - 1)/bands);
-				if((rc = sl->band_rows.reserve(band_items*sizeof(uint32_t)))){ return rc; }
-				if((rc = sl->band_loc.reserve((uint64_t)a.n_queries*(bands + 1)*sizeof(uint32_t)))){ return rc; }
-				if((rc = reserve_zeroed(sl->band_or, (uint64_t)a.n_queries*16*1024, gs))){ return rc; }
-				if((rc = reserve_zeroed(sl->band_state, (uint64_t)a.n_queries*sizeof(uint32_t), gs))){ return rc; }
-				ba.orbuf = (uint32_t*)sl->band_or.p;
-				ba.state = (uint32_t*)sl->band_state.p;
-				uint32_t *loc = (uint32_t*)sl->band_loc.p, *rows2 = (uint32_t*)sl->band_rows.p;
-				KW_GATHER_LAUNCH(ge, true, false, band_bucket_kernel, dim3(a.n_queries), dim3(256), 0, gs, a.rows, a.pos_off, a.nkmer, a.num_hash,
-				                 ba.bands, ba.rows_per_band, loc, rows2);
-				WalkArgs wb;
-				wb.total_slots = walk_slots;                         // (one column tile: slots = positions)
-				wb.per_wave = (walk_slots + waves - 1)/waves;
-				wb.coltiles = 1;
-				wb.orbuf = nullptr; wb.done = nullptr;
-				a.segs = 1;
-				a.chunks = 1;
-				snprintf(sl->kernel_name, sizeof(sl->kernel_name), "and_band_walk_kernel<%u,4>", walk_ch);
-				const dim3 grid(wgs), block(shape.wg_waves*WAVE), fgrid((a.n_queries + 3)/4);
-#define KWAGE_BAND_LAUNCH(CH, U) do { \
-					if(shape.lds > 48*1024){ (void)hipFuncSetAttribute((const void*)and_band_walk_kernel<CH, U>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shape.lds); } \
-					KW_GATHER_LAUNCH(ge, false, false, (and_band_walk_kernel<CH, U>), grid, block, shape.lds, gs, a, ba, wb, (const uint32_t*)rows2, (const uint32_t*)loc, a.pos_off, a.nkmer); \
-					KW_GATHER_LAUNCH(ge, false, true, (and_band_finish_kernel<CH>), fgrid, dim3(256), 0, gs, a, ba, a.nkmer); } while(0)
-#define KWAGE_BAND_CASE(CH) case CH: \
-					KWAGE_BAND_LAUNCH(CH, 4); break;
-				switch(walk_ch){
-					KWAGE_BAND_CASE(3) KWAGE_BAND_CASE(4) KWAGE_BAND_CASE(5) KWAGE_BAND_CASE(6) KWAGE_BAND_CASE(7)
-					KWAGE_BAND_CASE(8) KWAGE_BAND_CASE(9) KWAGE_BAND_CASE(10) KWAGE_BAND_CASE(11) KWAGE_BAND_CASE(12)
-					KWAGE_BAND_CASE(13) KWAGE_BAND_CASE(14) KWAGE_BAND_CASE(15)
-					default: KWAGE_BAND_CASE(16)
-				}
-#undef KWAGE_BAND_CASE
-#undef KWAGE_BAND_LAUNCH
-				HIP_TRY(hipGetLastError());
-				return KWAGE_OK;
-			}
-			WalkArgs wa;
-			wa.total_slots = walk_slots;
-			wa.per_wave = (walk_slots + waves - 1)/waves;
-			wa.coltiles = coltiles;
-			// cut-pair slots: one per wave, 16 KiB each whatever CH is; the kernel leaves them zero
-			if((rc = reserve_zeroed(sl->walk_or, waves*16*1024, gs))){ return rc; }
-			if((rc = reserve_zeroed(sl->walk_done, waves*2*sizeof(uint32_t), gs))){ return rc; }
-			wa.orbuf = (uint32_t*)sl->walk_or.p;
-			wa.done = (uint32_t*)sl->walk_done.p;
-			a.segs = 1;
-			a.chunks = coltiles;
-			snprintf(sl->kernel_name, sizeof(sl->kernel_name), "and_walk_kernel<%u,%d>", walk_ch, walk_unroll);
-			const dim3 grid(wgs), block(shape.wg_waves*WAVE);
-#define KWAGE_WALK_LAUNCH(...) do { \
-				if(shape.lds > 48*1024){ (void)hipFuncSetAttribute((const void*)and_walk_kernel<__VA_ARGS__>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shape.lds); } \
-				KW_GATHER_LAUNCH(ge, true, true, (and_walk_kernel<__VA_ARGS__>), grid, block, shape.lds, gs, a, wa, a.rows, a.pos_off, a.nkmer); } while(0)
-#define KWAGE_WALK_CASE(CH) case CH: KWAGE_WALK_LAUNCH(CH, 4); break;
-#define KWAGE_WALK_CASE8(CH) case CH: KWAGE_WALK_LAUNCH(CH, 8); break;
-			switch(walk_ch){
-				KWAGE_WALK_CASE8(1) KWAGE_WALK_CASE8(2) KWAGE_WALK_CASE(3) KWAGE_WALK_CASE(4) KWAGE_WALK_CASE(5) KWAGE_WALK_CASE(6) KWAGE_WALK_CASE(7)
-				KWAGE_WALK_CASE(8) KWAGE_WALK_CASE(9) KWAGE_WALK_CASE(10) KWAGE_WALK_CASE(11) KWAGE_WALK_CASE(12)
-				KWAGE_WALK_CASE(13) KWAGE_WALK_CASE(14) KWAGE_WALK_CASE(15)
-				default: KWAGE_WALK_CASE(16)
-			}
-#undef KWAGE_WALK_CASE8
-#undef KWAGE_WALK_CASE
-#undef KWAGE_WALK_LAUNCH
-			HIP_TRY(hipGetLastError());
-			return KWAGE_OK;
-		}
-		if(a.segs > 1){
-			const uint64_t bytes = (uint64_t)a.n_queries*g->stride;
-			if((rc = sl->partial.reserve(bytes))){ return rc; }
-			HIP_TRY(hipMemsetAsync(sl->partial.p, 0xFF, bytes, gs));
-			a.partial = (uint32_t*)sl->partial.p;
-		}
-		snprintf(sl->kernel_name, sizeof(sl->kernel_name), "and_kernel<%d,8,nt>%s", cfg.vec, a.segs > 1 ? "+segments" : "");      // (shape: vectors per lane, rows in flight, nontemporal)
-		launch_and_v(a, gs, cfg, ge);
-		if(a.segs > 1){
-			KW_GATHER_LAUNCH(ge, false, true, and_combine_kernel, dim3((a.units_per_row + 255)/256, a.n_queries), dim3(256), 0, gs, a);
-		}
-	}
-	else{
-		a.chunks = (a.units_per_row + WAVE - 1)/WAVE;
-		// counter planes: enough bits for the largest possible num_query_kmer of the batch
-		const uint32_t planes = planes_for(L->max_pos);
-		const bool narrow = tn.narrow && a.units_per_row <= 32 && a.units_per_row > 8 && a.n_queries >= 64 && planes <= 14;
-		// The persistent form (count_walk_kernel): equal shares of the batch's (query, KiB tile, position) list per wave,
-		// pairs cut by share boundaries added up as a tree through memory.  Taken when the batch gives every wave of the
-		// launch its 64 rows and no early exit is asked for (a persistent wave has no tile of its own to give up): long
-		// queries need no segment slab and no combine pass then (1 x 100 kb: 5410 vs 4813 GB/s, 4 x 1 Mb: 6431 vs 5705),
-		// no batch size ends in a part-filled round of waves, and in a host's software pipeline its resident waves do not
-		// share the CUs with the next batch's k-mer stage the way the tiled kernel's 13 000 workgroups do (C2 at t = 0.8
-		// inside bench.py: 1.988 vs 2.077 ms, profiles/r03_c2t_bench_ab.txt).  (Alone on the chip, batches whose tiles
-		// all fit in one round are 2-3 % faster through the tiled kernel -- 300 queries 0.582 vs 0.598 ms --: not worth
-		// a rule of their own.)  Early exit, tiny batches and forced segment counts go on below.
-		// early exit on rows of a KiB and more, enough (query, KiB tile) pairs to keep a persistent grid busy: screen, then refine
-		// (kernels.hpp count_screen_kernel).  Few long queries stay with the segments below: every tile has to read the first
-		// (1 - t) n k-mers before the bound can prune anything, and a handful of tiles that long would be the whole launch.
-		if(a.early_exit && tn.ee_refine && !narrow && tn.force_segs <= 0 && a.units_per_row >= WAVE
-		   && (uint64_t)a.n_queries*a.chunks >= (uint64_t)std::max<int64_t>(tn.count_screen_min_tiles, 1) && planes <= 14){      // (queries of up to 16383 positions: 20 and 32 counter planes + eight rows in flight do not fit a wave's registers)
-			const uint64_t tiles = (uint64_t)a.n_queries*a.chunks;
-			// k-mers per unit: 64 (7 counter planes per unit); queries above 8192 positions: 1/128 of the longest (14 planes)
-			uint32_t seg = (uint32_t)std::min<int64_t>(std::max<int64_t>(tn.refine_seg_rows, 8), 120)/8*8;
-			int up = 7;
-			if(L->max_pos > 8192){ seg = (uint32_t)((L->max_pos + 127)/128 + 7)/8*8; up = 14; }
-			// (as many waves as the kernel's registers let a CU hold -- knob count_screen_wpc caps it; they draw their tiles from a queue)
-			const uint64_t wpc = std::min<uint64_t>((uint64_t)std::max<int64_t>(tn.count_screen_wpc, 1), 4ull*count_screen_blocks_per_cu(planes, std::min(a.num_hash, 5u)));
-			const uint64_t screen_waves = (std::min<uint64_t>(tiles, ncu*wpc) + 3)/4*4;
-			if((rc = check_refine_units(planes, up))){ return rc; }
-			RefineSetup rs;
-			if((rc = refine_setup(sl, tn, a, L->total_pos, 0, seg, (uint64_t)planes*128, (uint64_t)up*128, tiles, screen_waves, ncu, gs, &rs))){ return rc; }
-			rs.ra.seg_rows = seg;
-			a.segs = 1;
-			snprintf(sl->kernel_name, sizeof(sl->kernel_name), "count_screen_kernel<%u,%u>+refine<%d>", planes, std::min(a.num_hash, 5u), up);
-			const dim3 grid((uint32_t)(screen_waves/4)), block(SEARCH_THREADS);
-			by_planes_to_14(planes, [&](auto P) {
-				by_nh(a.num_hash, [&](auto NH) {
-					KW_GATHER_LAUNCH(ge, true, false, (count_screen_kernel<decltype(P)::value, decltype(NH)::value>), grid, block, 0, gs, a, rs.ra);
+	switch(p.form){
+		case SearchForm::AND_NARROW:
+			by_int<16, 8, 4, 2>((int)p.G, [&](auto G) {
+				by_int<16, 8>(p.unroll, [&](auto U) {
+					KW_GATHER_LAUNCH(ge, true, true, (and_narrow_kernel<decltype(G)::value, decltype(U)::value>), grid, block, 0, gs, a);
 				});
 			});
-			launch_count_refine_and_emit(planes, up, a, rs, gs, ge);
-			HIP_TRY(hipGetLastError());
-			return KWAGE_OK;
+			break;
+		case SearchForm::AND_SCREEN: {
+			RefineArgs ra;
+			if((rc = refine_setup(sl, p.refine, gs, &ra))){ return rc; }
+			by_int<2, 1>(p.vec, [&](auto V) { KW_GATHER_LAUNCH(ge, true, false, (and_screen_kernel<decltype(V)::value, 8>), grid, block, 0, gs, a, ra); });
+			by_int<16, 8>(p.unroll, [&](auto U) { KW_GATHER_LAUNCH(ge, false, false, (and_refine_kernel<decltype(U)::value>), dim3(p.refine.refine_wgs), block, 0, gs, a, ra); });
+			KW_GATHER_LAUNCH(ge, false, true, and_refine_emit_kernel, dim3(p.refine.emit_wgs), block, 0, gs, a, ra);
+			break;
 		}
-		// Early exit over FEW LONG queries (fewer tiles than the screen form wants, or more counter planes than it holds): every
-		// tile has to read the first (1 - t) n k-mers plus a margin before kwage.cpp:478-481 can rule anything out, and a handful of
-		// tiles that long would be the whole launch -- so that part is walked by the BALANCED persistent count kernel over the
-		// first kcut(q) k-mers of every query (count_walk_kernel<.., TRUNC>), the columns that can still reach the threshold are
-		// handed over with their counters, and the refine launch counts their remaining k-mers in 128-byte groups.  kcut comes
-		// from the density of the matrix's DENSEST column (sampled at finalize): the smallest K with  K - (n - thr)  >=  pm K + 4.5 sqrt(pm (1 - pm) K) + 8,
-		// pm = that density ^ num_hash -- an estimate that decides how much is read, never what is reported.
-		if(a.early_exit && tn.ee_refine && tn.count_trunc && tn.count_walk && !narrow && tn.force_segs <= 0 && a.units_per_row >= WAVE && L->total_pos > 0){
-			const uint32_t nq = a.n_queries;
-			const uint32_t tplanes = std::max<uint32_t>(planes, 10);      // (no 7-plane instantiation of this form)
-			// The DENSEST column decides: a 128-byte group stays alive while any of its 1024 columns can still reach the threshold,
-			// and columns are not equally dense (every sample's filter has its own fill; the synthetic workloads' planted columns
-			// are 15 % denser than the rest).  + 3 sigma of what 4096 sampled rows can say about one column.
-			const double col = std::min(1.0, std::max(0.0, g->density_max) + 3.0*std::sqrt(0.25/4096.0));
-			const double pm = std::min(0.9, std::max(0.0005, std::pow(col, (double)a.num_hash)));
-			static const bool trunc_debug = getenv("KWAGE_TRUNC_DEBUG") != nullptr;
-			if(trunc_debug){ fprintf(stderr, "[kwage_amd] truncated count walk: sampled density %.5f, densest column %.5f, per-k-mer match probability planned with %.5f\n", g->density, g->density_max, pm); }
-			if((rc = sl->trunc_host.reserve(((uint64_t)nq + 1)*sizeof(uint64_t) + (uint64_t)nq*sizeof(uint32_t)))){ return rc; }
-			uint64_t *h_soff = (uint64_t*)sl->trunc_host.p;
-			uint32_t *h_kcut = (uint32_t*)(h_soff + nq + 1);
-			uint64_t walked = 0, max_rest = 0, rest_total = 0;
-			h_soff[0] = 0;
-			for(uint32_t i = 0; i < nq; ++i){
-				const uint64_t npos = L->h_pos_off[i + 1] - L->h_pos_off[i];
-				uint64_t kc = npos;
-				if(npos >= 64){
-					const uint32_t thr = (uint32_t)(threshold*(float)npos);      // kwage.cpp:388 on the positions (an upper bound of the distinct k-mers)
-					const double need = (double)(npos - std::min<uint64_t>(thr, npos));
-					double K = (need + 8.0)/(1.0 - pm);
-					for(int it = 0; it < 8; ++it){ K = (need + 8.0 + 4.5*std::sqrt(pm*(1.0 - pm)*K))/(1.0 - pm); }
-					const uint64_t k8 = ((uint64_t)K + 7)/8*8;
-					if(k8*20 <= npos*17){ kc = k8; }                              // (worth it when at least 15 % of the list is left out)
-				}
-				h_kcut[i] = (uint32_t)kc;
-				h_soff[i + 1] = h_soff[i] + kc;
-				walked += kc;
-				max_rest = std::max(max_rest, npos - kc);
-				rest_total += npos - kc;
+		case SearchForm::AND_BAND_WALK: {
+			BandArgs ba;
+			ba.bands = p.bands;
+			ba.rows_per_band = p.rows_per_band;
+			if((rc = sl->band_rows.reserve(p.band_rows_bytes))){ return rc; }
+			if((rc = sl->band_loc.reserve(p.band_loc_bytes))){ return rc; }
+			if((rc = reserve_zeroed(sl->band_or, p.exchange_bytes, gs))){ return rc; }
+			if((rc = reserve_zeroed(sl->band_state, p.flags_bytes, gs))){ return rc; }
+			ba.orbuf = (uint32_t*)sl->band_or.p;
+			ba.state = (uint32_t*)sl->band_state.p;
+			uint32_t *loc = (uint32_t*)sl->band_loc.p, *rows2 = (uint32_t*)sl->band_rows.p;
+			KW_GATHER_LAUNCH(ge, true, false, band_bucket_kernel, dim3(a.n_queries), dim3(256), 0, gs, a.rows, a.pos_off, a.nkmer, a.num_hash,
+			                 ba.bands, ba.rows_per_band, loc, rows2);
+			WalkArgs wb;
+			wb.total_slots = p.total_slots;                      // (one column tile: slots = positions)
+			wb.per_wave = p.per_wave;
+			wb.coltiles = 1;
+			wb.orbuf = nullptr; wb.done = nullptr;
+			// (the band kernels are instantiated for 3..16 KiB-steps, four rows in flight)
+			by_int<3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16>((int)p.ch, [&](auto C) {
+				constexpr int CH = decltype(C)::value;
+				if(p.lds > 48*1024){ (void)hipFuncSetAttribute((const void*)and_band_walk_kernel<CH, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds); }
+				KW_GATHER_LAUNCH(ge, false, false, (and_band_walk_kernel<CH, 4>), grid, block, p.lds, gs, a, ba, wb, (const uint32_t*)rows2, (const uint32_t*)loc, a.pos_off, a.nkmer);
+				KW_GATHER_LAUNCH(ge, false, true, (and_band_finish_kernel<CH>), dim3(p.finish_wgs), dim3(256), 0, gs, a, ba, a.nkmer);
+			});
+			break;
+		}
+		case SearchForm::AND_WALK: {
+			WalkArgs wa;
+			wa.total_slots = p.total_slots;
+			wa.per_wave = p.per_wave;
+			wa.coltiles = p.chunks;
+			if((rc = reserve_zeroed(sl->walk_or, p.exchange_bytes, gs))){ return rc; }
+			if((rc = reserve_zeroed(sl->walk_done, p.flags_bytes, gs))){ return rc; }
+			wa.orbuf = (uint32_t*)sl->walk_or.p;
+			wa.done = (uint32_t*)sl->walk_done.p;
+			by_ch(p.ch, [&](auto C) {
+				constexpr int CH = decltype(C)::value, U = (CH <= 2) ? 8 : 4;      // (the instantiated pairs: the plan's unroll)
+				if(p.lds > 48*1024){ (void)hipFuncSetAttribute((const void*)and_walk_kernel<CH, U>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds); }
+				KW_GATHER_LAUNCH(ge, true, true, (and_walk_kernel<CH, U>), grid, block, p.lds, gs, a, wa, a.rows, a.pos_off, a.nkmer);
+			});
+			break;
+		}
+		case SearchForm::AND_TILED:
+			if(p.segs > 1){
+				if((rc = sl->partial.reserve(p.partial_bytes))){ return rc; }
+				HIP_TRY(hipMemsetAsync(sl->partial.p, 0xFF, p.partial_bytes, gs));
+				a.partial = (uint32_t*)sl->partial.p;
 			}
-			const uint64_t slots = (uint64_t)a.chunks*walked;
-			const uint64_t chip_waves = ncu*(uint64_t)std::max<int64_t>(tn.count_walk_wpc, 1);
-			const uint64_t min_rows = (tn.count_walk_min_rows >= 0) ? (uint64_t)tn.count_walk_min_rows : (uint64_t)WALK_MIN_ROWS_PER_WAVE*chip_waves;
-			// units of 1/128 of the longest remainder (at least refine_seg_rows k-mers): 7 counter planes per unit up to 120 k-mers, 14 beyond
-			uint64_t seg = (uint64_t)std::min<int64_t>(std::max<int64_t>(tn.refine_seg_rows, 8), 120)/8*8;
-			seg = std::max<uint64_t>(seg, ((max_rest + 127)/128 + 7)/8*8);
-			const int up = (seg <= 120) ? 7 : 14;
-			uint64_t units_worst = 0;
-			for(uint32_t i = 0; i < nq && seg; ++i){
-				const uint64_t rest = (L->h_pos_off[i + 1] - L->h_pos_off[i]) - h_kcut[i];
-				units_worst += (uint64_t)a.chunks*8*((rest + seg - 1)/seg);
+			launch_and(p, a, gs, ge);
+			if(p.segs > 1){
+				KW_GATHER_LAUNCH(ge, false, true, and_combine_kernel, dim3(p.combine_wgs, a.n_queries), dim3(256), 0, gs, a);
 			}
-			// Lists: a place for every pair and every 128-byte group of it (few tiles: that is affordable), and for the units
-			// as many as a GiB of partial counters holds -- every group of every pair surviving is not what they are sized for;
-			// a pair that finds them full is counted to the end by the wave that holds it (count_walk_kernel).
-			const uint64_t tiles = (uint64_t)nq*a.chunks;
-			const uint64_t units_cap = std::max<uint64_t>(4096, std::min<uint64_t>(units_worst, (1ull << 30)/((uint64_t)up*128 + sizeof(RefineUnit))));
-			if(walked*10 <= L->total_pos*7 && slots*a.num_hash >= min_rows && seg <= 16376 && rest_total > 0 && tiles*8*(uint64_t)tplanes*128 <= (1ull << 30)){
-				const uint64_t want_waves = (tn.count_walk_waves > 0) ? std::min<uint64_t>((uint64_t)tn.count_walk_waves, slots)
-					: std::max<uint64_t>(1, std::min<uint64_t>(chip_waves, slots*a.num_hash/WALK_MIN_ROWS_PER_WAVE));
-				const WalkShape shape = walk_shape(tn, want_waves, ncu);
-				const uint64_t waves = (uint64_t)shape.wgs*shape.wg_waves;
-				if((rc = check_refine_units(tplanes, up))){ return rc; }
-				RefineSetup rs;
-				if((rc = refine_setup(sl, tn, a, rest_total, 0, (uint32_t)seg, (uint64_t)tplanes*128, (uint64_t)up*128, tiles, waves, ncu, gs, &rs, tiles, tiles*8, units_cap))){ return rc; }
-				rs.ra.seg_rows = (uint32_t)seg;
-				if((rc = sl->trunc_dev.reserve(((uint64_t)nq + 1)*sizeof(uint64_t) + (uint64_t)nq*sizeof(uint32_t)))){ return rc; }
-				HIP_TRY(hipMemcpyAsync(sl->trunc_dev.p, sl->trunc_host.p, ((uint64_t)nq + 1)*sizeof(uint64_t) + (uint64_t)nq*sizeof(uint32_t), hipMemcpyHostToDevice, gs));
-				CountWalkArgs wa;
-				wa.total_slots = slots;
-				wa.per_wave = (slots + waves - 1)/waves;
-				wa.coltiles = a.chunks;
-				if((rc = sl->cwalk_slab.reserve(waves*2*tplanes*1024))){ return rc; }
-				if((rc = reserve_zeroed(sl->cwalk_arrived, waves*CWALK_LEVELS*sizeof(uint32_t), gs))){ return rc; }
-				wa.slab = (uint32_t*)sl->cwalk_slab.p;
-				wa.arrived = (uint32_t*)sl->cwalk_arrived.p;
-				wa.slot_off = (const uint64_t*)sl->trunc_dev.p;
-				wa.kcut = (const uint32_t*)((const uint64_t*)sl->trunc_dev.p + nq + 1);
-				a.segs = 1;
-				snprintf(sl->kernel_name, sizeof(sl->kernel_name), "count_walk_kernel<%u,%u,trunc>+refine<%d>", tplanes, std::min(a.num_hash, 5u), up);
-				launch_count_walk<true>(tplanes, a, wa, rs.ra, shape, gs, ge);
-				launch_count_refine_and_emit(tplanes, up, a, rs, gs, ge);
+			break;
+		case SearchForm::COUNT_SCREEN: {
+			RefineArgs ra;
+			if((rc = refine_setup(sl, p.refine, gs, &ra))){ return rc; }
+			by_planes_to_14(p.planes, [&](auto P) {
+				by_nh(a.num_hash, [&](auto NH) {
+					KW_GATHER_LAUNCH(ge, true, false, (count_screen_kernel<decltype(P)::value, decltype(NH)::value>), grid, block, 0, gs, a, ra);
+				});
+			});
+			launch_count_refine_and_emit(p.planes, p, a, ra, gs, ge);
+			break;
+		}
+		case SearchForm::COUNT_WALK_TRUNC: {
+			RefineArgs ra;
+			if((rc = refine_setup(sl, p.refine, gs, &ra))){ return rc; }
+			if((rc = sl->trunc_dev.reserve(p.trunc_bytes))){ return rc; }
+			HIP_TRY(hipMemcpyAsync(sl->trunc_dev.p, sl->trunc_host.p, p.trunc_bytes, hipMemcpyHostToDevice, gs));
+			CountWalkArgs wa;
+			if((rc = count_walk_setup(sl, p, gs, &wa))){ return rc; }
+			wa.slot_off = (const uint64_t*)sl->trunc_dev.p;
+			wa.kcut = (const uint32_t*)((const uint64_t*)sl->trunc_dev.p + a.n_queries + 1);
+			launch_count_walk<true>(p, p.tplanes, a, wa, ra, gs, ge);
+			launch_count_refine_and_emit(p.tplanes, p, a, ra, gs, ge);
+			break;
+		}
+		case SearchForm::COUNT_WALK: {
+			CountWalkArgs wa;
+			if((rc = count_walk_setup(sl, p, gs, &wa))){ return rc; }
+			launch_count_walk<false>(p, p.planes, a, wa, RefineArgs(), gs, ge);
+			break;
+		}
+		case SearchForm::COUNT_NARROW:
+			by_int<4, 2>((int)p.G, [&](auto G) {
+				by_planes_to_14(p.planes, [&](auto P) {
+					by_nh(a.num_hash, [&](auto NH) {
+						KW_GATHER_LAUNCH(ge, true, true, (count_narrow_kernel<decltype(P)::value, decltype(NH)::value, decltype(G)::value>), grid, block, 0, gs, a);
+					});
+				});
+			});
+			break;
+		case SearchForm::COUNT_TILED:
+			if(p.segs > 1){
+				if((rc = sl->partial.reserve(p.partial_bytes))){ return rc; }
+				a.partial = (uint32_t*)sl->partial.p;
+			}
+			launch_count(p, a, gs, ge);
+			if(p.segs > 1){
 				HIP_TRY(hipGetLastError());
-				return KWAGE_OK;
+				if((rc = launch_count_combine(p, a, gs, ge))){ return rc; }
 			}
-		}
-		if(tn.count_walk && !a.early_exit && !narrow && tn.force_segs <= 0 && L->total_pos > 0){
-			const uint64_t slots = (uint64_t)a.chunks*L->total_pos;
-			const uint64_t chip_waves = ncu*(uint64_t)std::max<int64_t>(tn.count_walk_wpc, 1);
-			const uint64_t min_rows = (tn.count_walk_min_rows >= 0) ? (uint64_t)tn.count_walk_min_rows : (uint64_t)WALK_MIN_ROWS_PER_WAVE*chip_waves;
-			const uint64_t want_waves = (tn.count_walk_waves > 0) ? std::min<uint64_t>((uint64_t)tn.count_walk_waves, slots)
-				: std::max<uint64_t>(1, std::min<uint64_t>(chip_waves, slots*a.num_hash/WALK_MIN_ROWS_PER_WAVE));
-			const WalkShape shape = walk_shape(tn, want_waves, ncu);
-			const uint64_t waves = (uint64_t)shape.wgs*shape.wg_waves;
-			if(slots*a.num_hash >= min_rows){
-				CountWalkArgs wa;
-				wa.total_slots = slots;
-				wa.per_wave = (slots + waves - 1)/waves;
-				wa.coltiles = a.chunks;
-				if((rc = sl->cwalk_slab.reserve(waves*2*planes*1024))){ return rc; }
-				if((rc = reserve_zeroed(sl->cwalk_arrived, waves*CWALK_LEVELS*sizeof(uint32_t), gs))){ return rc; }
-				wa.slab = (uint32_t*)sl->cwalk_slab.p;
-				wa.arrived = (uint32_t*)sl->cwalk_arrived.p;
-				a.segs = 1;
-				// (shape: planes, hashes, the next step's rows prefetched, eight k-mers per step with 14 planes and more)
-				snprintf(sl->kernel_name, sizeof(sl->kernel_name), "count_walk_kernel<%u,%u,pf%s>", planes, std::min(a.num_hash, 5u), planes >= 14 ? ",8" : "");
-				wa.slot_off = nullptr; wa.kcut = nullptr;
-				launch_count_walk<false>(planes, a, wa, RefineArgs(), shape, gs, ge);
-				HIP_TRY(hipGetLastError());
-				return KWAGE_OK;
-			}
-		}
-		// Long queries: segments of the k-mer list are counted by different waves into a slab of partial counters
-		// and added by count_combine_kernel (a tree per (query, 64 units)); a segment's counters need only the
-		// planes its own k-mer count can reach.
-		choose_segments(a, L->max_pos, max_segments(a, 1024), tn.force_segs);
-		uint32_t seg_planes = (a.segs > 1) ? planes_for(a.seg_kmers) : planes;
-		// keep the slab of partial counters bounded (1 GiB)
-		while(a.segs > 1 && (uint64_t)a.n_queries*a.segs*seg_planes*g->stride > (1ull << 30)){
-			const uint64_t want = a.segs/2;
-			a.seg_kmers = (uint32_t)((L->max_pos + want - 1)/std::max<uint64_t>(want, 1));
-			a.segs = (uint32_t)((L->max_pos + a.seg_kmers - 1)/a.seg_kmers);
-			seg_planes = (a.segs > 1) ? planes_for(a.seg_kmers) : planes;
-		}
-		if((uint64_t)a.n_queries*a.segs*a.chunks/4 + 1 > 0x7FFFFFFFull){ return fail(KWAGE_ERR_ARG, "batch too large for one launch"); }
-		if(a.segs > 1){
-			if((rc = sl->partial.reserve((uint64_t)a.n_queries*a.segs*seg_planes*g->stride))){ return rc; }
-			a.partial = (uint32_t*)sl->partial.p;
-		}
-		if(narrow && a.segs == 1){
-			// one reference file (<= 2048 columns = 16 units) or two: 4 resp. 2 queries per wave
-			const int kps = 8;
-			snprintf(sl->kernel_name, sizeof(sl->kernel_name), "count_narrow_kernel<%u,%u,%d,%d>", planes, a.num_hash, a.units_per_row <= 16 ? 4 : 2, kps);
-			if(a.units_per_row <= 16){ launch_count_narrow<4>(planes, a, gs, ge); }
-			else{ launch_count_narrow<2>(planes, a, gs, ge); }
-			HIP_TRY(hipGetLastError());
-			return KWAGE_OK;
-		}
-		if(a.segs > 1){
-			snprintf(sl->kernel_name, sizeof(sl->kernel_name), "count_kernel<%u,%u>+segments->%u", seg_planes, std::min(a.num_hash, 5u), planes);
-		}
-		else{
-			snprintf(sl->kernel_name, sizeof(sl->kernel_name), "count_kernel<%u,%u>", planes, std::min(a.num_hash, 5u));
-		}
-		launch_count(seg_planes, a, gs, ge);
-		if(a.segs > 1){
-			HIP_TRY(hipGetLastError());
-			if((rc = launch_count_combine(planes, a, seg_planes, gs, ge))){ return rc; }
-		}
+			break;
 	}
 	HIP_TRY(hipGetLastError());
 	return KWAGE_OK;

@@ -30,15 +30,14 @@
 
 #include "kwage_amd.h"
 #include "kmer_device.hpp"
+#include "tuning.hpp"        // WAVE, SEARCH_THREADS, WALK_WG_WAVES, BAND_MAX, CWALK_LEVELS: shared with the host-side plan
 
 namespace kwage {
 
-static constexpr int WAVE = 64;
 static constexpr int KM_THREADS = 256;               // largest k-mer workgroup; short queries use 64 or 128
 static constexpr uint32_t KM_LDS_SLOTS = 4096;      // 32 KiB of u64 slots: queries up to 2048 positions
 static constexpr uint32_t KM_CHUNK = 1024;          // positions per workgroup of a long query (4 tiles of 256)
 static constexpr uint64_t KM_EMPTY = ~0ull;         // never a canonical word: min(w, rc) < all-ones
-static constexpr int SEARCH_THREADS = 256;          // 4 waves, one tile each
 
 // (2-bit packing + MurmurHash3 device helpers: kmer_device.hpp)
 
@@ -848,7 +847,6 @@ __global__ __launch_bounds__(SEARCH_THREADS) void and_refine_kernel(SearchArgs a
 //     `orbuf` -- and adds its k-mer count to the slot's counter; the wave whose add completes the pair's nkmer
 //     reads the result back, emits, and leaves slot, flags and counter ZERO again: the buffers are cleared
 //     once when they are allocated, never per search.
-static constexpr int WALK_WG_WAVES = 8;        // waves per workgroup (= per CU) of a chip-filling launch of the persistent kernels
 static constexpr uint32_t WALK_DEAD = 1u;      // some part of the pair has an all-zero mask: nothing to report
 static constexpr uint32_t WALK_DIRTY = 2u;     // some part ORed its mask into the slot: clear it when the pair is done
 
@@ -1051,7 +1049,6 @@ struct BandArgs {
 	uint32_t *orbuf;                // [n_queries][CH*4*64] complemented partial masks; zero between searches
 	uint32_t *state;                // [n_queries] WALK_DEAD | WALK_DIRTY; zero between searches
 };
-static constexpr uint32_t BAND_MAX = 64;
 
 // (band_bucket_kernel: engine.hip)
 
@@ -1830,7 +1827,6 @@ __device__ __forceinline__ void count_kmers_prefetch(const uint8_t *db, uint64_t
 //     atomic and one load of PLANES KiB; a 1 Mb query spread over 80 waves is summed in 7 levels, not by one wave.
 // Everything the protocol exchanges goes through device-scope stores / atomics and loads (the XCDs' L2s are not
 // coherent with one another for plain accesses), ordered by waiting for the stores' acknowledgements (vmcnt).
-static constexpr uint32_t CWALK_LEVELS = 32;      // tree depth a 32-bit wave count can need
 
 struct CountWalkArgs {
 	uint64_t total_slots;           // column tiles per row x positions of the batch

@@ -8,7 +8,8 @@
 - CASES: what test_gpu_search_shapes.py runs -- group, batch, threshold, flags, knobs -- and the exact name each case must
   report.  test_search_shapes_ledger.py checks on CPU that the cases launch every instantiation of the gfx950 assembly.
 
-Group keys (built by test_gpu_search_shapes.py; W columns, 2^L rows, NH hashes):
+Group keys (GROUP_SHAPES; built by test_gpu_search_shapes.py; W columns, 2^L rows, NH hashes; group_fill: the share of set
+bits the common columns are drawn with):
   ("and", CH)          W = 8192 CH - 93: rows of CH KiB-steps, NH = 1 + (CH - 1) % 5, L = 12
   ("and_wide",)        W = 8192 * 17 - 93: rows above 16 KiB, NH = 2, L = 12
   ("and_narrow", G)    W = 997 / 1997 / 3997 for G = 8 / 4 / 2, NH = 3, L = 12
@@ -16,10 +17,15 @@ Group keys (built by test_gpu_search_shapes.py; W columns, 2^L rows, NH hashes):
   ("count_narrow", NH, G)  W = 1997 / 3997 for G = 4 / 2, L = 14
   ("count_dense", NH)  W = 997, L = 12, columns of all ones: counts above 2^20
 Batch keys: BATCH_MAX_POS gives each batch's longest query in k-mer positions (k = 31); "and_many" and "and_wide" are sized
-from the device's CU count (CU_SIZED).  The count batches c10, c14a and c20a sit at the lower edge of their counter width
+from the device's CU count (CU_SIZED, batch_size).  batch_seqs(key, ncu) makes a batch's sequences -- the GPU test searches
+them, test_search_plan.py feeds their lengths to the host-side plan (kwage_amd/csrc/search_plan.hpp).  The count batches c10, c14a and c20a sit at the lower edge of their counter width
 (128, 1024, 16384 positions): a column holding every k-mer of the longest query needs the width's top plane."""
 import re
 from collections import namedtuple
+
+import numpy as np
+
+from topk_reference import rand_seq
 
 GATHER_FAMILIES = frozenset({
     "and_kernel", "and_combine_kernel", "and_narrow_kernel", "and_walk_kernel", "and_screen_kernel", "and_refine_kernel",
@@ -42,7 +48,7 @@ NHS = (1, 2, 3, 4, 5)
 
 
 def planes_for(max_count):
-    """engine.hip planes_for: the narrowest counter width whose bits hold max_count."""
+    """search_plan.hpp planes_for: the narrowest counter width whose bits hold max_count."""
     bits = 1
     while bits < 32 and (max_count >> bits) != 0:
         bits += 1
@@ -85,7 +91,7 @@ def launched(name):
     raise ValueError("not a search_kernel name of engine.hip: %r" % name)
 
 
-# The format strings of launch_search_stage's snprintf(sl->kernel_name, ...) and the arguments each can be given.
+# The format strings of search_plan.hpp's format_search_name and the arguments each can be given.
 FORMATS = {
     "and_narrow_kernel<%u,%d>": ["and_narrow_kernel<%d,%d>" % (g, u) for g in (8, 4, 2) for u in (16, 8)],
     "and_screen_kernel<%d,8>+refine<%d>": ["and_screen_kernel<%d,8>+refine<%d>" % (v, u) for v in (1, 2) for u in (8, 16)],
@@ -116,7 +122,64 @@ BOTH = (0, EE)
 BATCH_MAX_POS = {"and": 370, "and_short": 100, "and_many": 100, "and_wide": 100,
                  "c7": 127, "c10": 128, "c14a": 1024, "c14b": 12000, "c20a": 16384, "c20b": 40000,
                  "c32r": (1 << 21) + 100, "c32": (1 << 21) + 100, "n7": 127, "n10": 1023, "n14": 3000}
-CU_SIZED = ("and_many", "and_wide")       # query counts from the device's CU count (test_gpu_search_shapes.batch_size)
+CU_SIZED = ("and_many", "and_wide")       # query counts from the device's CU count (batch_size)
+K = 31
+
+GROUP_SHAPES = {"and": lambda ch: (8192 * ch - 93, 1 + (ch - 1) % 5, 12), "and_wide": lambda: (8192 * 17 - 93, 2, 12),
+                "and_narrow": lambda g: ({8: 997, 4: 1997, 2: 3997}[g], 3, 12), "count": lambda nh: (8099, nh, 17),
+                "count_narrow": lambda nh, g: ({4: 1997, 2: 3997}[g], nh, 14), "count_dense": lambda nh: (997, nh, 12)}
+
+
+def group_shape(key):
+    """-> (W columns, NH hashes, L: 2^L rows) of the group `key`."""
+    return GROUP_SHAPES[key[0]](*key[1:])
+
+
+def group_fill(key):
+    """The probability the bits of the group's common columns are set with."""
+    return 0.25 if key[0].startswith("and") else (0.02, 0.14, 0.27, 0.38, 0.46)[group_shape(key)[1] - 1]
+
+
+def batch_size(ncu, key):
+    return {"and_many": 16 * ncu * 8, "and_wide": (8 * ncu + 4) // 5 + 8}[key]
+
+
+def _period_query(rng, npos, period):
+    unit = rand_seq(rng, period)
+    n = npos + K - 1
+    return (unit * (n // period + 1))[:n]
+
+
+def batch_seqs(key, ncu):
+    """-> (seqs, plant): the sequences of batch `key` on a device of ncu CUs, and the indices of those whose rows the groups
+    plant columns from.  A function of (key, ncu) only."""
+    mp = BATCH_MAX_POS[key]
+    rng = np.random.default_rng(mp + (1 if key == "c32r" else 0))       # (batches of one length share their pool)
+    longest = mp + K - 1
+    if key == "c32":
+        seqs = [rand_seq(rng, longest), rand_seq(rng, 500), "ACGT" * 10]
+        plant = [0, 1]
+    elif key == "c32r":
+        seqs = [_period_query(rng, mp, 4001), rand_seq(rng, 3000), rand_seq(rng, 800)]
+        plant = [0, 1, 2]
+    elif key.startswith("and") or key.startswith("n"):
+        pool = [rand_seq(rng, longest)] + [rand_seq(rng, int(rng.integers(K + 4, longest + 1))) for _ in range(28)]
+        pool += [rand_seq(rng, K), "", "ACGTN" * 4, pool[3][:40] + "N" + pool[3][41:], pool[5]]   # one k-mer, none, none, an N, repeated
+        n = batch_size(ncu, key) if key in CU_SIZED else {"and": len(pool), "and_short": 2000, "n7": 96, "n10": 96, "n14": 96}[key]
+        seqs = [pool[i % len(pool)] for i in range(n)]
+        plant = list(range(29))
+    else:           # the count batches: a few long queries, shorter ones and the edge queries
+        seqs = [rand_seq(rng, longest)]
+        for f in (0.9, 0.6, 0.3):
+            seqs.append(rand_seq(rng, max(int(longest * f), K + 70)))
+        base = seqs[1]
+        mutated = list(base)
+        for p in range(11, len(mutated), 97):            # substitutions: counts between the threshold and n
+            mutated[p] = "ACGT"[("ACGT".index(mutated[p]) + 1) % 4]
+        seqs += ["".join(mutated), rand_seq(rng, 100), rand_seq(rng, K), "", "N" * 60, seqs[2]]
+        plant = [0, 1, 2, 3, 5]
+    assert max(max(len(s) - K + 1, 0) for s in seqs) == mp, (key, mp)
+    return seqs, plant
 
 WALK = dict(walk=4, walk_min_rows=1, walk_min_kib=1, walk_bands=0)
 BAND = dict(walk=4, walk_min_rows=1, walk_min_kib=1, walk_bands=3, walk_bands_min_gib=0)

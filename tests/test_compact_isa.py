@@ -14,7 +14,7 @@ from conftest import ROOT
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 CSRC = os.path.join(ROOT, "kwage_amd", "csrc")
 ASM = os.path.join(ROOT, "kwage_amd", "lib", "asm", "compact-hip-amdgcn-amd-amdhsa-gfx950.s")
-SOURCES = ("compact.hip", "compact_kernels.hpp", "compact_plan.hpp", "save_plan.hpp", "engine_state.hpp")      # (the Makefile's asm_compact target)
+SOURCES = ("compact.hip", "compact_kernels.hpp", "compact_plan.hpp", "save_plan.hpp", "engine_state.hpp", "tuning.hpp")      # (the Makefile's asm_compact target)
 
 
 @pytest.fixture(scope="module")

@@ -12,7 +12,7 @@ from conftest import ROOT
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 CSRC = os.path.join(ROOT, "kwage_amd", "csrc")
 ASM = os.path.join(ROOT, "kwage_amd", "lib", "asm", "filterset-hip-amdgcn-amd-amdhsa-gfx950.s")
-SOURCES = ("filterset.hip", "filterset_kernels.hpp", "score_stage.hpp", "pool_blocks.hpp", "engine_state.hpp")      # (the Makefile's asm_filterset target)
+SOURCES = ("filterset.hip", "filterset_kernels.hpp", "score_stage.hpp", "pool_blocks.hpp", "engine_state.hpp", "tuning.hpp")      # (the Makefile's asm_filterset target)
 KERNELS = {"column_bits_kernel", "filter_count_kernel", "filter_scan_kernel", "filter_expand_kernel", "identity_rows_kernel"}
 
 

@@ -17,13 +17,13 @@ import numpy as np
 import pytest
 
 import search_shapes as ss
-from topk_reference import HIT_DTYPE, assert_hits_equal, pack_columns, rand_bits, rand_seq
+from topk_reference import HIT_DTYPE, assert_hits_equal, pack_columns, rand_bits
 
 pytestmark = pytest.mark.gpu
 
 FULL_GRID = os.environ.get("KWAGE_SEARCH_FULL_GRID", "0") == "1"
 SWEEP = (1.0, 0.9, 0.8, 0.5, 0.05)
-K = 31
+K = ss.K
 PERSISTENT = ("walk", "screen", "trunc", "refine")
 
 
@@ -79,44 +79,9 @@ class Env:
         return self.rows_cache[(seq, L)]
 
 
-def batch_size(env, key):
-    return {"and_many": 16 * env.ncu * 8, "and_wide": (8 * env.ncu + 4) // 5 + 8}[key]
-
-
-def _period_query(rng, npos, period):
-    unit = rand_seq(rng, period)
-    n = npos + K - 1
-    return (unit * (n // period + 1))[:n]
-
-
 class Batch:
     def __init__(self, env, key):
-        mp = ss.BATCH_MAX_POS[key]
-        rng = np.random.default_rng(mp + (1 if key == "c32r" else 0))       # (batches of one length share their pool)
-        longest = mp + K - 1
-        if key == "c32":
-            seqs = [rand_seq(rng, longest), rand_seq(rng, 500), "ACGT" * 10]
-            plant = [0, 1]
-        elif key == "c32r":
-            seqs = [_period_query(rng, mp, 4001), rand_seq(rng, 3000), rand_seq(rng, 800)]
-            plant = [0, 1, 2]
-        elif key.startswith("and") or key.startswith("n"):
-            pool = [rand_seq(rng, longest)] + [rand_seq(rng, int(rng.integers(K + 4, longest + 1))) for _ in range(28)]
-            pool += [rand_seq(rng, K), "", "ACGTN" * 4, pool[3][:40] + "N" + pool[3][41:], pool[5]]   # one k-mer, none, none, an N, repeated
-            n = batch_size(env, key) if key in ss.CU_SIZED else {"and": len(pool), "and_short": 2000, "n7": 96, "n10": 96, "n14": 96}[key]
-            seqs = [pool[i % len(pool)] for i in range(n)]
-            plant = list(range(29))
-        else:           # the count batches: a few long queries, shorter ones and the edge queries
-            seqs = [rand_seq(rng, longest)]
-            for f in (0.9, 0.6, 0.3):
-                seqs.append(rand_seq(rng, max(int(longest * f), K + 70)))
-            base = seqs[1]
-            mutated = list(base)
-            for p in range(11, len(mutated), 97):            # substitutions: counts between the threshold and n
-                mutated[p] = "ACGT"[("ACGT".index(mutated[p]) + 1) % 4]
-            seqs += ["".join(mutated), rand_seq(rng, 100), rand_seq(rng, K), "", "N" * 60, seqs[2]]
-            plant = [0, 1, 2, 3, 5]
-        assert max(max(len(s) - K + 1, 0) for s in seqs) == mp, (key, mp)
+        seqs, plant = ss.batch_seqs(key, env.ncu)
         self.key, self.seqs, self.plant = key, seqs, [seqs[i] for i in plant]
         self.b = env.ka.Batch(env.ctx, seqs)
         self.distinct = list(dict.fromkeys(seqs))
@@ -124,9 +89,6 @@ class Batch:
         self.nkmer = np.array([n[s] for s in seqs], dtype=np.uint32)
 
 
-GROUP_SHAPES = {"and": lambda ch: (8192 * ch - 93, 1 + (ch - 1) % 5, 12), "and_wide": lambda: (8192 * 17 - 93, 2, 12),
-                "and_narrow": lambda g: ({8: 997, 4: 1997, 2: 3997}[g], 3, 12), "count": lambda nh: (8099, nh, 17),
-                "count_narrow": lambda nh, g: ({4: 1997, 2: 3997}[g], nh, 14), "count_dense": lambda nh: (997, nh, 12)}
 GROUP_BATCHES = {"and": ("and",), "and_wide": ("and_wide",), "and_narrow": ("and_short",), "count": ("c7", "c10", "c14a", "c14b", "c20a", "c20b", "c32r"),
                  "count_narrow": ("n7", "n10", "n14"), "count_dense": ("c32",)}
 
@@ -135,12 +97,12 @@ class Group:
     def __init__(self, env, key):
         ka, oracle = env.ka, env.oracle
         rng = np.random.default_rng(7 + 131 * sum(map(ord, str(key))))
-        W, nh, L = GROUP_SHAPES[key[0]](*key[1:])
+        W, nh, L = ss.group_shape(key)
         self.key, self.W, self.nh, self.L = key, W, nh, L
         nrows, nb = 1 << L, (W + 7) // 8
         dense = key[0] == "count_dense"
         common = 8 if dense else 32                          # base bytes used all over the row
-        p = {"and": 0.25, "count": (0.02, 0.14, 0.27, 0.38, 0.46)[nh - 1]}["and" if key[0].startswith("and") else "count"]
+        p = ss.group_fill(key)
         # planted columns: (kind, rows), one base column each -- the unique base bytes follow the common ones
         planted = []
         t0s = (0.8, 0.9)

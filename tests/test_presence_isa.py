@@ -16,7 +16,7 @@ import presence_shapes as ps
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 CSRC = os.path.join(ROOT, "kwage_amd", "csrc")
 ASM = os.path.join(ROOT, "kwage_amd", "lib", "asm", "presence-hip-amdgcn-amd-amdhsa-gfx950.s")
-SOURCES = ("presence.hip", "presence_kernels.hpp", "tile_search.hpp", "pool_blocks.hpp", "engine_state.hpp", "kernels.hpp", "kmer_device.hpp")      # (the Makefile's asm_presence target)
+SOURCES = ("presence.hip", "presence_kernels.hpp", "tile_search.hpp", "pool_blocks.hpp", "engine_state.hpp", "tuning.hpp", "kernels.hpp", "kmer_device.hpp")      # (the Makefile's asm_presence target)
 BIT_FAMILIES = ("presence_tile_kernel", "presence_combine_kernel", "presence_and_kernel")
 FAMILIES = BIT_FAMILIES + ("presence_popcount_kernel",)
 

@@ -13,7 +13,7 @@ from conftest import ROOT
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 CSRC = os.path.join(ROOT, "kwage_amd", "csrc")
 ASM = os.path.join(ROOT, "kwage_amd", "lib", "asm", "save-hip-amdgcn-amd-amdhsa-gfx950.s")
-SOURCES = ("save.hip", "save_kernels.hpp", "save_plan.hpp", "db_writer.hpp", "bloom_files.hpp", "engine_state.hpp", "host.hpp")      # (the Makefile's asm_save target)
+SOURCES = ("save.hip", "save_kernels.hpp", "save_plan.hpp", "db_writer.hpp", "bloom_files.hpp", "engine_state.hpp", "tuning.hpp", "host.hpp")      # (the Makefile's asm_save target)
 WIDTHS = (16, 4, 1)
 
 

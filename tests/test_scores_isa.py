@@ -15,7 +15,7 @@ import scores_shapes as ss
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 CSRC = os.path.join(ROOT, "kwage_amd", "csrc")
 ASM = os.path.join(ROOT, "kwage_amd", "lib", "asm", "scores-hip-amdgcn-amd-amdhsa-gfx950.s")
-SOURCES = ("scores.hip", "scores_kernels.hpp", "tile_search.hpp", "score_stage.hpp", "pool_blocks.hpp", "engine_state.hpp", "kernels.hpp", "kmer_device.hpp")      # (the Makefile's asm_scores target)
+SOURCES = ("scores.hip", "scores_kernels.hpp", "tile_search.hpp", "score_stage.hpp", "pool_blocks.hpp", "engine_state.hpp", "tuning.hpp", "kernels.hpp", "kmer_device.hpp")      # (the Makefile's asm_scores target)
 FAMILIES = ("score_tile_kernel", "score_combine_kernel")
 
 

@@ -1,6 +1,6 @@
 """The ledger of tests/search_shapes.py against the gfx950 assembly of engine.hip (no GPU): the case table of
 test_gpu_search_shapes.py launches every gather-kernel instantiation the compiler emitted, every instantiation the ledger
-names exists, and every name engine.hip can report is understood.  An instantiation added without a case, a case lost,
+names exists, and every name the search can report (search_plan.hpp format_search_name) is understood.  An instantiation added without a case, a case lost,
 or an instantiation left behind that nothing launches fails here, naming it."""
 import os
 import re
@@ -12,7 +12,7 @@ import search_shapes as ss
 
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 CSRC = os.path.join(ROOT, "kwage_amd", "csrc")
-SOURCES = ("engine.hip", "engine_state.hpp", "kernels.hpp", "kmer_device.hpp")      # (the Makefile's asm target)
+SOURCES = ("engine.hip", "engine_state.hpp", "tuning.hpp", "kernels.hpp", "search_plan.hpp", "kmer_device.hpp")      # (the Makefile's asm target)
 
 
 def gather_instantiations():
@@ -45,8 +45,8 @@ def test_cases_launch_every_gather_instantiation():
 
 
 def test_every_printable_name_is_understood():
-    src = open(os.path.join(CSRC, "engine.hip")).read()
-    formats = set(re.findall(r'snprintf\(sl->kernel_name, sizeof\(sl->kernel_name\), "([^"]*)"', src))
+    src = open(os.path.join(CSRC, "search_plan.hpp")).read()
+    formats = set(re.findall(r'snprintf\(out, n, "([^"]*)"', src.split("inline void format_search_name(")[1]))
     assert formats == set(ss.FORMATS), (formats ^ set(ss.FORMATS))
     asm = gather_instantiations()
     for name in ss.printable_names():
@@ -63,7 +63,8 @@ def test_every_printable_name_is_understood():
 
 
 def test_case_names_follow_the_dispatch_rules():
-    """The names in CASES restate engine.hip's choices; pinned here where they are plain arithmetic."""
+    """The names in CASES restate search_plan.hpp's choices; pinned here where they are plain arithmetic (test_search_plan.py
+    runs the plan itself on every case)."""
     assert [ss.planes_for(n) for n in (1, 127, 128, 1023, 1024, 16383, 16384, (1 << 20) - 1, 1 << 20)] == [7, 7, 10, 10, 14, 14, 20, 20, 32]
     for c in ss.CASES:
         if c.test == "count_screen":
@@ -75,7 +76,7 @@ def test_case_names_follow_the_dispatch_rules():
 
 
 def test_refine_units_pair_with_fourteen_planes():
-    """engine.hip check_refine_units: 14-plane refine units go with an emit kernel of 14 planes or more, never another."""
+    """search_plan.hpp check_refine_units: 14-plane refine units go with an emit kernel of 14 planes or more, never another."""
     for name in ss.printable_names():
         for fam, a in ss.launched(name):
             if fam == "count_refine_emit_kernel" and a[1] == 14:
