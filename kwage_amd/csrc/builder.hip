@@ -18,6 +18,7 @@
 #include <zlib.h>
 
 #include "bloom_files.hpp"
+#include "build_plan.hpp"
 #include "db_writer.hpp"
 #include "host.hpp"
 #include "internal.h"
@@ -121,6 +122,15 @@ __global__ void pack_columns_kernel(uint32_t *dst, uint64_t dst_stride_words, ui
 	}
 }
 
+// KWAGE_BUILD_CHUNK_KB: the bytes a chunk's input and output may each take, in KiB, read per call; unset or 0: the plan's
+// default (256 MiB).  It changes how many chunks kwage_build_db and kwage_repack_db take, never the file they write.
+uint64_t build_budget_bytes()
+{
+	const char *v = getenv("KWAGE_BUILD_CHUNK_KB");
+	const long long kb = v ? atoll(v) : 0;
+	return kb > 0 ? (uint64_t)std::min<long long>(kb, 1ll << 40)*1024 : 0;
+}
+
 }  // namespace
 
 // The device context internals this file needs (defined in engine.hip).
@@ -154,18 +164,19 @@ extern "C" int kwage_build_db(kwage_ctx *ctx, const char *out_path, const kwage_
 	bool ok = fwrite(hdr, 1, sizeof(hdr), fout) == sizeof(hdr);
 
 	// ---- transpose, chunk by chunk --------------------------------------------------------------
-	// chunk rows: bounded so that the input (n x rows/8) and the output (rows x slice) both stay <= 256 MiB (the output is
-	// double-buffered: a chunk's CRC32 and file write run on a host thread beside the next chunk's gather, copies and kernel
-	// -- db_writer.hpp write_db_body)
-	uint64_t chunk_rows = filter_len;
-	while(chunk_rows > 1024 && (chunk_rows/8*n > (256ull << 20) || chunk_rows*slice_size > (256ull << 20))){ chunk_rows /= 2; }
-	// Filters lie `in_stride` apart in the device's input block, and a lane's 32 loads go to 32 consecutive filters at the
-	// same offset: with a power-of-two stride they all fall on the same few memory channels (3.87 TB/s in + out; a stride of
-	// an ODD number of 256-byte units: 4.43-4.50, profiles/r04_builder_transpose.txt).  KWAGE_BUILD_PAD = bytes added instead.
-	const uint64_t chunk_bytes = (chunk_rows + 7)/8;
-	uint64_t in_stride = (chunk_bytes + 255)/256*256;
-	if((in_stride/256) % 2 == 0){ in_stride += 256; }
-	if(const char *v = getenv("KWAGE_BUILD_PAD")){ in_stride = (chunk_bytes + 3)/4*4 + (uint64_t)std::max<long long>(atoll(v), 0)/4*4; }      // (never below the chunk itself)
+	// chunk rows: bounded so that the input (n x rows/8) and the output (rows x slice) both stay within the budget, 256 MiB
+	// (the output is double-buffered: a chunk's CRC32 and file write run on a host thread beside the next chunk's gather,
+	// copies and kernel -- db_writer.hpp write_db_body).  The rule, with the stride of the filters in the device's input
+	// block: build_plan.hpp.  KWAGE_BUILD_PAD = bytes added to the chunk's own instead of the odd-256-byte-unit rule;
+	// KWAGE_BUILD_CHUNK_KB = the budget in KiB (both read per call).
+	long long pad_bytes = -1;
+	if(const char *v = getenv("KWAGE_BUILD_PAD")){ pad_bytes = std::max<long long>(atoll(v), 0); }
+	const BuildChunks plan = plan_build_chunks(build_budget_bytes(), n, filter_len, pad_bytes);
+	const uint64_t chunk_rows = plan.chunk_rows, in_stride = plan.in_stride;
+	if(getenv("KWAGE_VERBOSE")){
+		fprintf(stderr, "[kwage] build_db: %llu chunks of %llu rows (filters %llu bytes apart)\n",
+		        (unsigned long long)plan.chunks, (unsigned long long)chunk_rows, (unsigned long long)in_stride);
+	}
 	void *d_in = nullptr, *d_out = nullptr, *h_in = nullptr;
 	hipError_t e = hipMalloc(&d_in, in_stride*n);
 	if(e == hipSuccess){ e = hipMalloc(&d_out, chunk_rows*slice_size); }
@@ -270,8 +281,11 @@ extern "C" int kwage_repack_db(kwage_ctx *ctx, const char *out_path, const char 
 	memset(hdr, 0, sizeof(hdr));
 	bool ok = fwrite(hdr, 1, sizeof(hdr), fout) == sizeof(hdr);
 
-	uint64_t chunk_rows = nrows;
-	while(chunk_rows > 1 && (chunk_rows*dst_words*4 > (256ull << 20) || chunk_rows*max_width > (256ull << 20))){ chunk_rows /= 2; }
+	const RepackChunks plan = plan_repack_chunks(build_budget_bytes(), nrows, dst_words, max_width);       // build_plan.hpp
+	const uint64_t chunk_rows = plan.chunk_rows;
+	if(getenv("KWAGE_VERBOSE")){
+		fprintf(stderr, "[kwage] repack_db: %llu chunks of %llu rows\n", (unsigned long long)plan.chunks, (unsigned long long)chunk_rows);
+	}
 	void *d_dst = nullptr, *d_src = nullptr, *h_buf = nullptr;
 	const uint64_t host_bytes = std::max(chunk_rows*dst_words*4, chunk_rows*max_width);
 	hipError_t e = hipMalloc(&d_dst, chunk_rows*dst_words*4);

@@ -101,7 +101,7 @@ def test_distinct_kmer_count_and_long_sequences(oracle):
         b.close()
         exp = len(np.unique(np.concatenate([oracle.unique_kmers(s, 31) for s in seqs if len(s) >= 31])))
         assert cnt.value == exp
-        # bits through make_bloom's internal chunking of the 300 kb sequence
+        # bits of the 300 kb sequence UNCUT: one workgroup walks it (kwage_make_bloom's piece cut: tests/bloom_shapes.py, group 6)
         prm = native.Params(31, 3, 22, 0)
         bits = np.zeros((1 << 22) // 8, dtype=np.uint8)
         b = ka.Batch(ctx, seqs)

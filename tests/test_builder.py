@@ -231,3 +231,114 @@ def test_dbtool_front_end(tmp_path):
     assert run("build", str(tmp_path / "g.db"), "21", "18", r.stderr.split("num_hash ")[1].split()[0], bl).returncode == 0
     assert run("repack", wide, a, os.path.join(GOLDEN, "k32", "k32.db")).returncode == 1      # different parameters
     assert run("nonsense", "x").returncode == 2
+
+
+# ---------------------------------------------------------------------------------------------
+# more than one chunk: KWAGE_BUILD_CHUNK_KB (read per call) replaces the 256 MiB budget of kwage_build_db and
+# kwage_repack_db (kwage_amd/csrc/build_plan.hpp; tests/test_build_plan.py pins the plan itself).  It changes how many
+# chunks are taken -- KWAGE_VERBOSE reports them -- never the file.
+# ---------------------------------------------------------------------------------------------
+def _chunks_reported(stderr, entry):
+    import re
+    found = re.findall(r"\[kwage\] %s: (\d+) chunks of (\d+) rows" % entry, stderr)
+    assert len(found) == 1, stderr[-800:]
+    return int(found[0][0]), int(found[0][1])
+
+
+_filter_sets = {}
+
+
+@pytest.fixture(scope="module")
+def filter_set(oracle, tmp_path_factory):
+    """(n, L) -> (paths of n random `.bloom` files of 2^L bits, the `.db` file the oracle builds of them): written once."""
+    def get(n, L):
+        if (n, L) not in _filter_sets:
+            d = tmp_path_factory.mktemp("filters_%d_%d" % (n, L))
+            rng = np.random.default_rng(1000 * n + L)
+            paths = []
+            for j in range(n):
+                p = str(d / ("f%04d.bloom" % j))
+                oracle.write_bloom(p, 21, L, 1, oracle.FilterInfo(run_accession=oracle.str_to_accession("SRR%d" % (j + 1))),
+                                   rng.integers(0, 256, size=(1 << L) // 8, dtype=np.uint8))
+                paths.append(p)
+            _filter_sets[n, L] = (paths, oracle.build_db_bytes(paths))
+        return _filter_sets[n, L]
+    return get
+
+
+# 1025 filters x 2^13 bits at 256 KiB: output rows of 129 bytes, the second filter tile holds ONE filter, two row tiles of 512
+# per chunk at the tiles of 512 rows, and every chunk but the first starts at r0 != 0 of every filter.  PAD=4: filters 132
+# bytes apart, a stride that is no multiple of 256.  300 x 2^12 at 64 KiB: a single, partial filter tile.  2500 x 2^11 at
+# 1 KiB: the floor of 1024 rows holds although neither buffer fits the budget.
+MULTI_CHUNK_BUILDS = [
+    ("default_tile", 1025, 13, {"KWAGE_BUILD_CHUNK_KB": "256"}, (8, 1024)),
+    ("tile1", 1025, 13, {"KWAGE_BUILD_CHUNK_KB": "256", "KWAGE_BUILD_TILE": "1"}, (8, 1024)),
+    ("tile2", 1025, 13, {"KWAGE_BUILD_CHUNK_KB": "256", "KWAGE_BUILD_TILE": "2"}, (8, 1024)),
+    ("tile3", 1025, 13, {"KWAGE_BUILD_CHUNK_KB": "256", "KWAGE_BUILD_TILE": "3"}, (8, 1024)),
+    ("pad4", 1025, 13, {"KWAGE_BUILD_CHUNK_KB": "256", "KWAGE_BUILD_PAD": "4"}, (8, 1024)),
+    ("n300", 300, 12, {"KWAGE_BUILD_CHUNK_KB": "64"}, (4, 1024)),
+    ("floor", 2500, 11, {"KWAGE_BUILD_CHUNK_KB": "1"}, (2, 1024)),
+]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name,n,L,env,chunks", MULTI_CHUNK_BUILDS, ids=[c[0] for c in MULTI_CHUNK_BUILDS])
+def test_builder_with_more_than_one_chunk(filter_set, tmp_path, name, n, L, env, chunks):
+    import subprocess
+    from kwage_amd import native
+    tool = os.path.join(os.path.dirname(native.KWAGE_BIN), "kwage_dbtool")
+    paths, want = filter_set(n, L)
+    out = str(tmp_path / "out.db")
+    clean = {k: v for k, v in os.environ.items() if not k.startswith("KWAGE_BUILD_")}
+    r = subprocess.run([tool, "build", out, "21", str(L), "1"] + paths, capture_output=True, text=True, env=dict(clean, KWAGE_VERBOSE="1", **env))
+    assert r.returncode == 0, r.stderr
+    assert _chunks_reported(r.stderr, "build_db") == chunks
+    assert open(out, "rb").read() == want
+
+
+def _ragged_parts(oracle, tmp_path):
+    """The six ragged inputs of test_repack_is_the_column_concatenation (236 columns, 1024 rows), the second one compressed."""
+    from kwage_amd import native
+    rng = np.random.default_rng(12)
+    paths = []
+    for f, n in enumerate((13, 21, 1, 64, 7, 130)):
+        bits = rng.random((1 << 10, ((n + 7) // 8) * 8)) < 0.3
+        bits[:, n:] = False
+        infos = [oracle.FilterInfo(run_accession=oracle.str_to_accession("ERR%d" % (100 * f + j + 1))) for j in range(n)]
+        p = str(tmp_path / ("part%d.db" % f))
+        oracle.write_db(p, 25, 2, 10, np.packbits(bits, axis=1, bitorder="little"), n, infos)
+        paths.append(p)
+    z = str(tmp_path / "part1.dbz")
+    native.check(native.lib().kwage_db_compress(paths[1].encode(), z.encode(), 2))
+    return paths, [paths[0], z] + paths[2:]
+
+
+@pytest.mark.gpu
+def test_repack_with_more_than_one_chunk(oracle, tmp_path):
+    """4 KiB: 8 chunks of 128 rows (236 columns = 8 dwords a row on the device).  Every source is read at r0 != 0, the compressed
+    one included, every source's CRC32 and the output's continue over the chunks, and the rows are stripped of their dword
+    padding (30 bytes of 32) chunk by chunk."""
+    import subprocess
+    from kwage_amd import native
+    tool = os.path.join(os.path.dirname(native.KWAGE_BIN), "kwage_dbtool")
+    paths, inputs = _ragged_parts(oracle, tmp_path)
+    clean = {k: v for k, v in os.environ.items() if not k.startswith("KWAGE_BUILD_")}
+    run = lambda out, ins, env: subprocess.run([tool, "repack", out] + ins, capture_output=True, text=True, env=dict(clean, KWAGE_VERBOSE="1", **env))
+    one, many = str(tmp_path / "one_chunk.db"), str(tmp_path / "wide.db")
+    r = run(one, inputs, {})
+    assert r.returncode == 0 and _chunks_reported(r.stderr, "repack_db") == (1, 1024), r.stderr
+    r = run(many, inputs, {"KWAGE_BUILD_CHUNK_KB": "4"})
+    assert r.returncode == 0 and _chunks_reported(r.stderr, "repack_db") == (8, 128), r.stderr
+    assert open(many, "rb").read() == open(one, "rb").read()
+    wide = oracle.read_db(many)                   # (what the file holds: test_repack_is_the_column_concatenation, on the same inputs)
+    assert wide.header.num_filter == 236 and wide.rows.shape == (1024, 30)
+    # a flipped byte in the LAST chunk of a source (row 1000 of 1024; 64 columns = 8 bytes a row behind the 44-byte header)
+    raw = bytearray(open(paths[3], "rb").read())
+    raw[44 + 8 * 1000 + 3] ^= 0x10
+    flipped = str(tmp_path / "flipped.db")
+    open(flipped, "wb").write(raw)
+    bad_out = str(tmp_path / "bad_crc.db")
+    r = run(bad_out, [paths[0], flipped], {"KWAGE_BUILD_CHUNK_KB": "4"})
+    assert r.returncode == 1 and "Invalid CRC32 value for source database file" in r.stderr, r.stderr
+    assert _chunks_reported(r.stderr, "repack_db")[0] > 1
+    assert not os.path.exists(bad_out)
