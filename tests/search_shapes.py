@@ -16,6 +16,7 @@ bits the common columns are drawn with):
   ("count", NH)        W = 8099 (one KiB-step, one column tile), L = 17
   ("count_narrow", NH, G)  W = 1997 / 3997 for G = 4 / 2, L = 14
   ("count_dense", NH)  W = 997, L = 12, columns of all ones: counts above 2^20
+  ("count_wide", NH)   W = 8192 * 3 - 93: three KiB-steps in front of the count kernels, L = 14 (search_holes.py's cases only)
 Batch keys: BATCH_MAX_POS gives each batch's longest query in k-mer positions (k = 31); "and_many" and "and_wide" are sized
 from the device's CU count (CU_SIZED, batch_size).  batch_seqs(key, ncu) makes a batch's sequences -- the GPU test searches
 them, test_search_plan.py feeds their lengths to the host-side plan (kwage_amd/csrc/search_plan.hpp).  The count batches c10, c14a and c20a sit at the lower edge of their counter width
@@ -127,7 +128,8 @@ K = 31
 
 GROUP_SHAPES = {"and": lambda ch: (8192 * ch - 93, 1 + (ch - 1) % 5, 12), "and_wide": lambda: (8192 * 17 - 93, 2, 12),
                 "and_narrow": lambda g: ({8: 997, 4: 1997, 2: 3997}[g], 3, 12), "count": lambda nh: (8099, nh, 17),
-                "count_narrow": lambda nh, g: ({4: 1997, 2: 3997}[g], nh, 14), "count_dense": lambda nh: (997, nh, 12)}
+                "count_narrow": lambda nh, g: ({4: 1997, 2: 3997}[g], nh, 14), "count_dense": lambda nh: (997, nh, 12),
+                "count_wide": lambda nh: (8192 * 3 - 93, nh, 14)}
 
 
 def group_shape(key):
@@ -138,6 +140,13 @@ def group_shape(key):
 def group_fill(key):
     """The probability the bits of the group's common columns are set with."""
     return 0.25 if key[0].startswith("and") else (0.02, 0.14, 0.27, 0.38, 0.46)[group_shape(key)[1] - 1]
+
+
+def planted_edges(nb):
+    """The bytes of a row of nb bytes that hold a group's planted columns first: the row's ends, the first unit boundary, the
+    first 128-byte boundary, the middle and both sides of every KiB-step boundary."""
+    edges = [0, 15, 16, 127, 128, nb // 2, nb - 1] + [j for s in range(1024, nb, 1024) for j in (s - 1, s)]
+    return list(dict.fromkeys(e for e in edges if 0 <= e < nb))
 
 
 def batch_size(ncu, key):

@@ -1,8 +1,8 @@
 """The host-side plan of the threshold search's gather stage (kwage_amd/csrc/search_plan.hpp: which form runs, its template
 integers, segments, launch shapes, list capacities, the truncated walk's tables, the reported name), built with
 g++ -fsanitize=address,undefined as a stand-alone program (tests/sanitize/search_plan_sanitize.cpp) that reads a file of
-cases and prints each plan.  Two sets of cases: every row of search_shapes.CASES on a device of 256 CUs must plan the
-name the GPU test asserts, and a few thousand pseudo-random inputs must keep the plan's invariants.  CPU only: no device
+cases and prints each plan.  Two sets of cases: every row of search_shapes.CASES (and of search_holes.WIDE_CASES) on a device
+of 256 CUs must plan the name the GPU test asserts, and a few thousand pseudo-random inputs must keep the plan's invariants.  CPU only: no device
 is touched, nothing is loaded into python."""
 import os
 import shutil
@@ -109,6 +109,24 @@ def test_every_case_plans_its_name(planner):
     for i, (ci, c, fl, dm) in enumerate(want):
         assert got[i]["rc"] == "0" and got[i]["name"] == c.name, (c, fl, dm, got[i])
     assert {ci for ci, _, _, _ in want} == set(range(len(ss.CASES)))
+
+
+def test_wide_count_cases_plan_their_names(planner):
+    """The cases search_holes.py adds to the table, on the group of three KiB-steps: the same inputs as above, the truncated
+    walk again at the fill and 0.05 above it."""
+    import search_holes as sh
+    lines, want = [], []
+    for c in sh.WIDE_CASES:
+        W, nh, L = ss.group_shape(c.group)
+        fill = ss.group_fill(c.group)
+        for fl in c.flags:
+            for dm in ((fill, fill + 0.05) if c.test == "count_walk_trunc" else (fill,)):
+                lines.append(case_line(NCU, sh.stride_bytes(W), 1 << L, nh, dm, c.t, fl, c.knobs, batch_runs(c.batch)))
+                want.append((c, fl, dm))
+    got = planner(lines, "wide.txt")
+    assert len(want) >= 10
+    for i, (c, fl, dm) in enumerate(want):
+        assert got[i]["rc"] == "0" and got[i]["name"] == c.name and got[i]["chunks"] == "3", (c, fl, dm, got[i])
 
 
 def test_plan_invariants_over_a_grid(planner):
