@@ -690,6 +690,40 @@ typedef struct {
 int kwage_group_save_db(kwage_group *g, const char *out_path, const kwage_save_column *cols, uint32_t n,
                         uint64_t staging_bytes, kwage_save_stats *stats);
 
+/* Export, no counterpart in the reference (which has dump_bloom / dump_db to look at such objects): `n` columns of the
+ * group's resident matrix handed back as what they were made from -- whole Bloom filters, filter-major, 2^L bits each,
+ * LSB first: the payload of a `.bloom` file, exactly the layout kwage_group_insert_filters and kwage_filterset_from_bits
+ * read -- transposed on the device.  The inverse of the live insert: a sample of a resident database can be moved to
+ * another group, re-inserted after a rebuild, or written as the `.bloom` file it was built from.
+ *   - columns[i] is a global column of the group and becomes filter i of the output; the list may be in any order and may
+ *     name a column more than once (it is then written more than once);
+ *   - filter i lies at bits + i*filter_stride_bytes (the stride is ignored when n < 2) and is max(1, 2^L / 8) bytes; for
+ *     L < 3 it is one byte whose bits at and above 2^L are written as zero.  Exactly the filters' bytes are written:
+ *     nothing between or behind them is touched, and nothing has to be cleared beforehand.  One thread owns an (output
+ *     filter, 32 rows): no atomics, no read of the output;
+ *   - the group, its matrix, valid mask and span are not changed; before and after kwage_group_finalize;
+ *   - flags: KWAGE_SEARCH_TIMING fills *export_kernel_ms (may be NULL) with the HIP-event duration of the export kernels
+ *     summed over chunks; other bits are ignored.
+ * The host form stages chunks of rows -- rows [r0, r0 + nr), nr a multiple of 8 -- through the context's load buffer;
+ * a chunk's n x nr/8 bytes leave the device with one strided copy, to bits + i*filter_stride_bytes + r0/8.  staging_bytes
+ * bounds a chunk: 0 means 64 MiB, and any value works, down to one byte of every filter per chunk.  The device form
+ * writes device memory in place; pointer and stride must be multiples of 4.  The file form writes n `.bloom` files (magic,
+ * the group's BloomParam, CRC32 of the bits, FilterInfo record, bits), filter i to out_paths[i]; the record comes from
+ * cols[i] exactly as kwage_group_save_db takes it.  Every file is written under a temporary name beside its destination
+ * and all n are renamed only once all are complete: a failure on the device or on disk leaves no partial file, no
+ * temporary file, and an existing destination as it was.
+ * Errors, all found before a byte of the caller's memory or of any file is written: KWAGE_ERR_ARG for a NULL argument,
+ * n == 0, a sparse group, a column at or beyond the span, a pad or retired column, a filter_stride_bytes smaller than a
+ * filter with n > 1, a device pointer or stride that is not a multiple of 4, an entry with neither source_db nor info, a
+ * source_column beyond its file, a NULL path; KWAGE_ERR_STATE while a search is pending on the context; KWAGE_ERR_IO /
+ * KWAGE_ERR_FORMAT for an unreadable or damaged source of metadata.  Synchronous; runs on the context's first stream. */
+int kwage_group_export_filters(kwage_group *g, const uint64_t *columns, uint32_t n, void *bits,
+                               uint64_t filter_stride_bytes, uint64_t staging_bytes, uint32_t flags, float *export_kernel_ms);
+int kwage_group_export_filters_device(kwage_group *g, const uint64_t *columns, uint32_t n, void *bits_dev,
+                                      uint64_t filter_stride_bytes, uint32_t flags, float *export_kernel_ms);
+int kwage_group_export_bloom_files(kwage_group *g, const kwage_save_column *cols, const char *const *out_paths, uint32_t n,
+                                   uint64_t staging_bytes, uint32_t flags, float *export_kernel_ms);
+
 /* ------------------------------------------------------------------------------------
  * Host-side helpers that mirror the reference's host code for this path (no device needed).
  * ---------------------------------------------------------------------------------- */

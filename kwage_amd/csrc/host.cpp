@@ -895,15 +895,22 @@ int sample_info_to_filter_info(const kwage_sample_info *si, FilterInfo &fi)
 	return KWAGE_OK;
 }
 
+// What a `.bloom` file holds before its FilterInfo record: the magic, the BloomParam and the CRC32 of the bits, the last
+// four of the BLOOM_FILE_HEAD_BYTES (= 21) bytes appended to `head`.
+void bloom_file_head(const kwage_params *params, uint32_t crc, std::vector<unsigned char> &head)
+{
+	head.push_back(0xFF);                                               // BLOOM_MAGIC_COMPLETE, bloom.h:28
+	auto u32 = [&](uint32_t v) { for(int i = 0; i < 4; ++i){ head.push_back((unsigned char)(v >> (8*i))); } };
+	u32(params->kmer_len); u32(params->log_2_filter_len); u32(params->num_hash); u32((uint32_t)params->hash_func);   // bloom.h:550-554
+	u32(crc);                                                                                                          // bloom.cpp:328-343
+}
+
 // binary_write<BloomFilter> (binary_io.cpp:182-208)
 int write_bloom_file(const char *out_path, const kwage_params *params, const FilterInfo &fi,
                      const unsigned char *bits, uint64_t nbytes)
 {
 	std::vector<unsigned char> head;
-	head.push_back(0xFF);                                               // BLOOM_MAGIC_COMPLETE, bloom.h:28
-	auto u32 = [&](uint32_t v) { for(int i = 0; i < 4; ++i){ head.push_back((unsigned char)(v >> (8*i))); } };
-	u32(params->kmer_len); u32(params->log_2_filter_len); u32(params->num_hash); u32((uint32_t)params->hash_func);   // bloom.h:550-554
-	u32((uint32_t)crc32_z(crc32_z(0L, Z_NULL, 0), bits, nbytes));                                                      // bloom.cpp:328-343
+	bloom_file_head(params, (uint32_t)crc32_z(crc32_z(0L, Z_NULL, 0), bits, nbytes), head);
 	pack_filter_info(fi, head);
 	FILE *f = fopen(out_path, "wb");
 	if(!f){ return fail(KWAGE_ERR_IO, "Unable to open %s for writing", out_path); }

@@ -13,6 +13,11 @@
 //                                                                   `.bloom` files, without the ones in.db was built from
 //   kwage_dbtool drop <out.db> <in.db> <run accession>...           in.db without the listed samples; exit code 1 when one of
 //                                                                   them is not in the file
+//   kwage_dbtool extract <out dir> <in.db> [<run accession>...]     in.db loaded into a group, the named samples (none named:
+//                                                                   all, in column order) written back as the `.bloom` files
+//                                                                   they were built from, <out dir>/<accession>.bloom
+//                                                                   (kwage_group_export_bloom_files), records copied verbatim;
+//                                                                   exit code 1, nothing written, when one is not in the file
 //   kwage_dbtool mkbloom <out.bloom> <accession> <k> <log2 len|0> <num hash|0> <seq file> [p]
 //                                                                   exact k-mer set of a FASTA/FASTQ -> .bloom; 0 0 = pick the
 //                                                                   parameters with optimal_bloom_param(p, default 0.25)
@@ -26,6 +31,7 @@
 #include <string>
 #include <vector>
 
+#include <sys/stat.h>
 #include <unistd.h>
 
 #include "kwage_amd.h"
@@ -45,6 +51,7 @@ static int usage()
 		"       kwage_dbtool repack <out.db> <in.db>...\n"
 		"       kwage_dbtool append <out.db> <in.db> <x.bloom>...\n"
 		"       kwage_dbtool drop <out.db> <in.db> <run accession>...\n"
+		"       kwage_dbtool extract <out dir> <in.db> [<run accession>...]\n"
 		"       kwage_dbtool mkbloom <out.bloom> <accession> <k> <log2 len|0> <num hash|0> <seq file> [p]\n"
 		"       kwage_dbtool countbloom <out.bloom> <accession> <k> <min count> <seq file>... [-p p] [-l min log2] [-L max log2]\n");
 	return 2;
@@ -95,11 +102,12 @@ static int append_blooms(kwage_ctx *ctx, const char *out_db, const char *in_db, 
 	return rc;
 }
 
-static int drop_samples(kwage_ctx *ctx, const char *out_db, const char *in_db, char **accessions, int n)
+// The run accession of every column of in_db; every one of the n `accessions` must be among them (else exit code 1).
+static int read_accessions(const char *what, const char *in_db, char **accessions, int n, std::vector<std::string> &have)
 {
 	kwage_dbinfo *d = NULL;
 	if(kwage_dbinfo_open(in_db, &d)){ return die("read metadata"); }
-	std::vector<std::string> have(kwage_dbinfo_num_filter(d));
+	have.assign(kwage_dbinfo_num_filter(d), std::string());
 	char buf[64];
 	for(uint32_t j = 0; j < have.size(); ++j){
 		if(kwage_dbinfo_csv_string(d, j, buf, sizeof(buf))){ kwage_dbinfo_close(d); return die("read FilterInfo"); }
@@ -109,12 +117,19 @@ static int drop_samples(kwage_ctx *ctx, const char *out_db, const char *in_db, c
 	for(int i = 0; i < n; ++i){
 		bool found = false;
 		for(const std::string &a : have){ found = found || a == accessions[i]; }
-		if(!found){ fprintf(stderr, "kwage_dbtool: drop: %s holds no sample with run accession %s\n", in_db, accessions[i]); return 1; }
+		if(!found){ fprintf(stderr, "kwage_dbtool: %s: %s holds no sample with run accession %s\n", what, in_db, accessions[i]); return 1; }
 	}
+	return 0;
+}
+
+static int drop_samples(kwage_ctx *ctx, const char *out_db, const char *in_db, char **accessions, int n)
+{
+	std::vector<std::string> have;
+	int rc = read_accessions("drop", in_db, accessions, n, have);
+	if(rc){ return rc; }
 	kwage_db_header h;
 	kwage_group *g = NULL;
-	int rc = load_db(ctx, in_db, 0, &h, &g);
-	if(rc){ return rc; }
+	if((rc = load_db(ctx, in_db, 0, &h, &g))){ return rc; }
 	std::vector<kwage_save_column> cols;
 	for(uint32_t j = 0; j < have.size(); ++j){
 		bool gone = false;
@@ -122,6 +137,36 @@ static int drop_samples(kwage_ctx *ctx, const char *out_db, const char *in_db, c
 		if(!gone){ cols.push_back(kwage_save_column{j, in_db, j, NULL}); }
 	}
 	rc = save_columns(g, out_db, cols);
+	kwage_group_destroy(g);
+	return rc;
+}
+
+static int extract_samples(kwage_ctx *ctx, const char *out_dir, const char *in_db, char **accessions, int n)
+{
+	std::vector<std::string> have;
+	int rc = read_accessions("extract", in_db, accessions, n, have);
+	if(rc){ return rc; }
+	// the named samples in the order named (the first column that carries the accession), or every column
+	std::vector<kwage_save_column> cols;
+	std::vector<std::string> paths;
+	auto take = [&](uint32_t j) {
+		cols.push_back(kwage_save_column{j, in_db, j, NULL});
+		paths.push_back(std::string(out_dir) + "/" + have[j] + ".bloom");
+	};
+	if(n == 0){ for(uint32_t j = 0; j < have.size(); ++j){ take(j); } }
+	for(int i = 0; i < n; ++i){
+		for(uint32_t j = 0; j < have.size(); ++j){ if(have[j] == accessions[i]){ take(j); break; } }
+	}
+	if(cols.empty()){ fprintf(stderr, "kwage_dbtool: extract: %s holds no sample\n", in_db); return 1; }
+	kwage_db_header h;
+	kwage_group *g = NULL;
+	if((rc = load_db(ctx, in_db, 0, &h, &g))){ return rc; }
+	(void)mkdir(out_dir, 0777);                       // (it may exist)
+	std::vector<const char*> out(paths.size());
+	for(size_t i = 0; i < paths.size(); ++i){ out[i] = paths[i].c_str(); }
+	float ms = 0;
+	if(kwage_group_export_bloom_files(g, cols.data(), out.data(), (uint32_t)cols.size(), 0, KWAGE_SEARCH_TIMING, &ms)){ rc = die("extract"); }
+	else{ fprintf(stderr, "wrote %zu .bloom files to %s, export kernel %.3f ms\n", cols.size(), out_dir, ms); }
 	kwage_group_destroy(g);
 	return rc;
 }
@@ -158,7 +203,7 @@ int main(int argc, char **argv)
 	}
 
 	// the remaining commands run on the device
-	if(cmd != "build" && cmd != "repack" && cmd != "append" && cmd != "drop" && cmd != "mkbloom" && cmd != "countbloom"){ return usage(); }
+	if(cmd != "build" && cmd != "repack" && cmd != "append" && cmd != "drop" && cmd != "extract" && cmd != "mkbloom" && cmd != "countbloom"){ return usage(); }
 	kwage_ctx *ctx = NULL;
 	const char *dev = getenv("KWAGE_DEVICE");
 	if(kwage_init(dev ? atoi(dev) : 0, &ctx)){ return die("init"); }
@@ -179,6 +224,9 @@ int main(int argc, char **argv)
 	}
 	else if(cmd == "drop" && argc >= 5){
 		rc = drop_samples(ctx, argv[2], argv[3], argv + 4, argc - 4);
+	}
+	else if(cmd == "extract" && argc >= 4){
+		rc = extract_samples(ctx, argv[2], argv[3], argv + 4, argc - 4);
 	}
 	else if(cmd == "mkbloom" && argc >= 8){
 		kwage_seqfile *sf = NULL;

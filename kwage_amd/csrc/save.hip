@@ -12,8 +12,6 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
-#include <map>
-#include <memory>
 #include <string>
 #include <vector>
 
@@ -24,54 +22,11 @@
 #include "host.hpp"
 #include "save_kernels.hpp"
 #include "save_plan.hpp"
+#include "save_records.hpp"
 
 using namespace kwage;
 
-// host.cpp
-namespace kwage { int sample_info_to_filter_info(const kwage_sample_info *si, FilterInfo &fi); }
-
 namespace {
-
-// The FilterInfo record of every listed column, one after the other in list order: copied verbatim from its `.db` /
-// `.dbz` file (each distinct file opened once), or serialized from a kwage_sample_info as kwage_make_bloom does.
-int collect_records(const kwage_save_column *cols, uint32_t n, std::vector<uint64_t> &rec_len, std::vector<unsigned char> &recs)
-{
-	const char *who = "kwage_group_save_db";
-	std::map<std::string, std::unique_ptr<DbInfo>> sources;
-	rec_len.assign(n, 0);
-	recs.clear();
-	for(uint32_t i = 0; i < n; ++i){
-		const kwage_save_column &c = cols[i];
-		if(c.source_db){
-			std::unique_ptr<DbInfo> &d = sources[c.source_db];
-			if(!d){
-				d.reset(new DbInfo());
-				std::string err;
-				if(!d->open(c.source_db, err) || !d->load(err)){ return fail(KWAGE_ERR_IO, "%s: %s", who, err.c_str()); }
-			}
-			if(c.source_column >= d->header.num_filter){
-				return fail(KWAGE_ERR_ARG, "%s: entry %u: %s has no column %u", who, i, c.source_db, c.source_column);
-			}
-			const uint64_t l = d->info_loc[c.source_column];
-			if(l < d->tail_start || l >= d->tail_start + d->tail.size()){ return fail(KWAGE_ERR_FORMAT, "%s: %s: bad metadata index", who, c.source_db); }
-			const unsigned char *p = d->tail.data() + (l - d->tail_start);
-			FilterInfo fi;
-			size_t used = 0;
-			if(!parse_filter_info(p, d->tail.size() - (l - d->tail_start), fi, &used)){ return fail(KWAGE_ERR_FORMAT, "%s: %s: bad FilterInfo record", who, c.source_db); }
-			recs.insert(recs.end(), p, p + used);
-			rec_len[i] = used;
-		}
-		else{
-			FilterInfo fi;
-			int rc = sample_info_to_filter_info(c.info, fi);
-			if(rc){ return rc; }
-			const size_t before = recs.size();
-			pack_filter_info(fi, recs);
-			rec_len[i] = recs.size() - before;
-		}
-	}
-	return KWAGE_OK;
-}
 
 // extract_columns_kernel over one chunk of rows, queued on `stream`.
 hipError_t launch_extract(const kwage_group *g, const SaveRun *d_runs, uint32_t n_runs, uint32_t n, uint64_t r0, uint64_t nr,
@@ -115,7 +70,7 @@ extern "C" int kwage_group_save_db(kwage_group *g, const char *out_path, const k
 	if(ch.chunks > 0xFFFFFFFFull){ return fail(KWAGE_ERR_ARG, "%s: staging_bytes %llu cuts the file into too many chunks", who, (unsigned long long)staging_bytes); }
 	std::vector<uint64_t> rec_len;
 	std::vector<unsigned char> recs;
-	if((rc = collect_records(cols, n, rec_len, recs))){ return rc; }
+	if((rc = collect_records(who, cols, n, rec_len, recs))){ return rc; }
 	if((rc = set_device(ctx))){ return rc; }
 
 	// the device side: the run table and one chunk of output

@@ -234,15 +234,14 @@ class Group:
         self._column_bits = None
         return new, {f: getattr(st, f) for f, _ in native.CompactStats._fields_}
 
-    def save_db(self, path: str, columns: Sequence[int], sources: Sequence, staging_bytes: int = 0) -> dict:
-        """Write the listed columns, in list order, as one raw `.db` file (kwage_group_save_db): gathered and packed on the
-        device, byte for byte what kwage_build_db writes from the same filters.  sources[i] says where column i's
-        FilterInfo record comes from: (db_path, column) copies it from that file, a dict of kwage_sample_info fields
-        (at least run_accession) serializes it.  Returns the call's stats."""
+    @staticmethod
+    def _save_columns(columns: Sequence[int], sources: Sequence):
+        """The kwage_save_column array of save_db() and export_bloom_files(): (array, what its entries point to -- to be
+        kept alive until the call returns)."""
         n = len(columns)
         assert len(sources) == n, (len(sources), n)
         cols = (native.SaveColumn * max(n, 1))()
-        keep = []                                    # what the entries point to, alive until the call returns
+        keep = []
         for i, (c, src) in enumerate(zip(columns, sources)):
             cols[i].column = int(c)
             if isinstance(src, dict):
@@ -259,9 +258,53 @@ class Group:
             elif src is not None:
                 cols[i].source_db = str(src[0]).encode()
                 cols[i].source_column = int(src[1])
+        return cols, keep
+
+    def save_db(self, path: str, columns: Sequence[int], sources: Sequence, staging_bytes: int = 0) -> dict:
+        """Write the listed columns, in list order, as one raw `.db` file (kwage_group_save_db): gathered and packed on the
+        device, byte for byte what kwage_build_db writes from the same filters.  sources[i] says where column i's
+        FilterInfo record comes from: (db_path, column) copies it from that file, a dict of kwage_sample_info fields
+        (at least run_accession) serializes it.  Returns the call's stats."""
+        n = len(columns)
+        cols, keep = self._save_columns(columns, sources)      # (keep: alive until the call returns)
         st = native.SaveStats()
         check(lib().kwage_group_save_db(self._h, path.encode(), cols, n, staging_bytes, C.byref(st)))
         return {"db_bytes": st.db_bytes, "runs": st.runs, "chunks": st.chunks, "extract_kernel_ms": st.extract_kernel_ms}
+
+    def export_filters(self, cols: Sequence[int], out=None, staging_bytes: int = 0, timing: bool = False):
+        """Export (kwage_group_export_filters): the listed columns, in list order (any order, repeats allowed), handed back
+        as whole Bloom filters -- uint8 [n, max(1, 2^L / 8)], LSB first: `.bloom` payloads, what insert_filters() and
+        FilterSet.from_bits() read -- transposed on the device.  out=None returns a new numpy array; a numpy `out` takes
+        the host form (rows may lie further apart than a filter), a CUDA uint8 tensor `out` the device form; exactly the
+        filters' bytes of `out` are written.  Returns the array (with timing=True: (array, kernel ms))."""
+        cols = np.ascontiguousarray(cols, dtype=np.uint64)
+        n, fb = int(cols.size), max(1, self._nrows // 8)
+        ms = C.c_float(0)
+        flags = SEARCH_TIMING if timing else 0
+        cptr = cols.ctypes.data_as(C.POINTER(C.c_uint64)) if n else None
+        if out is None:
+            out = np.empty((n, fb), dtype=np.uint8)
+        if isinstance(out, np.ndarray):
+            assert out.dtype == np.uint8 and out.ndim == 2 and out.shape[0] == n and out.shape[1] >= fb, out.shape
+            assert out.shape[0] <= 1 or out.strides[1] == 1 and out.strides[0] >= out.shape[1], out.strides
+            assert out.flags.writeable and (out.shape[0] == 0 or out.strides[1] == 1), "export_filters: a writable uint8 [n, bytes] array"
+            check(lib().kwage_group_export_filters(self._h, cptr, n, out.ctypes.data if out.size else None, out.strides[0], staging_bytes, flags, C.byref(ms)))
+        else:
+            import torch
+            assert out.is_cuda and out.dtype == torch.uint8 and out.dim() == 2 and out.shape[0] == n and (out.shape[1] <= 1 or out.stride(1) == 1), "export_filters: a uint8 [n, bytes] CUDA tensor"
+            assert out.shape[1] >= fb, out.shape
+            check(lib().kwage_group_export_filters_device(self._h, cptr, n, out.data_ptr() if out.numel() else None, out.stride(0), flags, C.byref(ms)))
+        return (out, ms.value) if timing else out
+
+    def export_bloom_files(self, cols: Sequence[int], sources: Sequence, paths: Sequence[str], staging_bytes: int = 0) -> None:
+        """Write the listed columns as `.bloom` files (kwage_group_export_bloom_files), column cols[i] to paths[i]: what
+        kwage_build_db, insert_bloom_files() and `kwage_dbtool append` read.  sources as in save_db().  All files appear
+        together once all are complete; a failure leaves none."""
+        n = len(cols)
+        assert len(paths) == n, (len(paths), n)
+        sc, keep = self._save_columns(cols, sources)      # (keep: alive until the call returns)
+        arr = (C.c_char_p * max(n, 1))(*[None if p is None else str(p).encode() for p in paths])
+        check(lib().kwage_group_export_bloom_files(self._h, sc, arr, n, staging_bytes, 0, None))
 
     def set_bits(self, rows: np.ndarray, columns: np.ndarray) -> None:
         rows = np.ascontiguousarray(rows, dtype=np.uint32)
@@ -979,6 +1022,30 @@ class FileDatabase(Database):
                 out = os.path.join(out_dir, "k%d_L%d_h%d_f%d_%04d.db" % (p.kmer_len, p.log_2_filter_len, p.num_hash, p.hash_func, part))
                 g.save_db(out, [c for c, _ in piece], [s for _, s in piece])
                 written.append(out)
+        return written
+
+    def export_samples(self, accessions: Sequence[str], out_dir: str) -> List[str]:
+        """Write samples of the resident database back as the `.bloom` files they were built from
+        (Group.export_bloom_files): for each accession the first sample in report order carrying it, as
+        <out_dir>/<accession>.bloom.  A file sample takes the record of its own file; a live sample gets its recorded run
+        accession and no other field (save()'s rule).  KeyError, before anything is written, when no sample carries an
+        accession.  Returns the files written."""
+        import os
+        first = {}
+        for gi, col, path, c in self._samples():
+            first.setdefault(self._accession(path, c), (gi, col, path, c))
+        for a in accessions:
+            if a not in first:
+                raise KeyError("no sample with run accession %s in the database" % a)
+        os.makedirs(out_dir, exist_ok=True)
+        written = []
+        for gi, g in enumerate(self.groups):
+            mine = [(a,) + first[a][1:] for a in accessions if first[a][0] == gi]
+            if mine:
+                paths = [os.path.join(out_dir, a + ".bloom") for a, _, _, _ in mine]
+                g.export_bloom_files([col for _, col, _, _ in mine],
+                                     [{"run_accession": path.accessions[c]} if isinstance(path, _LiveBlock) else (path, c) for _, _, path, c in mine], paths)
+                written.extend(paths)
         return written
 
     def _accession(self, path: str, column: int) -> str:

@@ -208,6 +208,9 @@ _SIGNATURES = [
     ("kwage_bloom_counter_finish", C.c_int, [_P, C.c_float, C.c_uint32, C.POINTER(SampleInfo), C.c_char_p, C.POINTER(Params), C.POINTER(C.c_int)]),
     ("kwage_repack_db", C.c_int, [_P, C.c_char_p, C.POINTER(C.c_char_p), C.c_uint32]),
     ("kwage_group_save_db", C.c_int, [_P, C.c_char_p, C.POINTER(SaveColumn), C.c_uint32, C.c_uint64, C.POINTER(SaveStats)]),
+    ("kwage_group_export_filters", C.c_int, [_P, C.POINTER(C.c_uint64), C.c_uint32, _P, C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(C.c_float)]),
+    ("kwage_group_export_filters_device", C.c_int, [_P, C.POINTER(C.c_uint64), C.c_uint32, _P, C.c_uint64, C.c_uint32, C.POINTER(C.c_float)]),
+    ("kwage_group_export_bloom_files", C.c_int, [_P, C.POINTER(SaveColumn), C.POINTER(C.c_char_p), C.c_uint32, C.c_uint64, C.c_uint32, C.POINTER(C.c_float)]),
     ("kwage_db_read_header", C.c_int, [C.c_char_p, C.POINTER(DbHeader)]),
     ("kwage_db_read_slices", C.c_int, [C.c_char_p, C.POINTER(C.c_uint32), C.c_uint64, C.c_void_p]),
     ("kwage_db_compress", C.c_int, [C.c_char_p, C.c_char_p, C.c_uint32]),
