@@ -155,7 +155,11 @@ void kwage_set_load_progress(kwage_ctx *ctx, volatile uint64_t *bytes_passed);
 int kwage_group_add_random_columns(kwage_group *g, uint64_t num_columns, uint64_t seed,
                                    uint32_t density_q8, uint64_t *first_column);
 
-/* Set individual bits (planting known positives into a synthetic database). */
+/* Set individual bits (planting known positives into a synthetic database).  Any column below the span is accepted, a
+ * pad or retired column too: every reader masks those by the valid mask, so such bits change no result.  Bits planted in
+ * the (up to seven) pad columns between an open tail and the span stay in memory until the next live insert, which
+ * continues at the tail, overwrites them -- a kwage_group_compact with nothing to close does not clear them.  The bit
+ * densities a finalized group plans its early exit with are NOT re-sampled (planning inputs: they change no result). */
 int kwage_group_set_bits(kwage_group *g, const uint32_t *rows, const uint64_t *columns, uint64_t n);
 
 /* Copy `n` whole rows (row_bytes() bytes each) back to the host, `out_stride` bytes apart. */
@@ -236,7 +240,8 @@ int kwage_group_retire_columns(kwage_group *g, const uint64_t *columns, uint64_t
  * afterwards the matrix is bit for bit what ONE call of the host form of the live insert, given the survivors at
  * column 0, would have made.
  *   - the span becomes 8 * ceil(m / 8), row_bytes = ceil(m / 8); bits m .. span - 1 of every row are zero, and so is
- *     everything from there up to the old span; the valid mask holds exactly bits [0, m); the column count, the row
+ *     everything from there up to the old span (where the call rewrites rows at all: a group with nothing to close is the
+ *     exception, below); the valid mask holds exactly bits [0, m); the column count, the row
  *     stride, the allocation and the row count stay; the tail is open at column m, so the next live insert continues
  *     there at bit granularity and the freed capacity is available at once;
  *   - before and after the finalize call; a finalized group stays finalized and re-samples its bit densities as the live
@@ -248,7 +253,10 @@ int kwage_group_retire_columns(kwage_group *g, const uint64_t *columns, uint64_t
  *     units: a segment's units are all made in registers before any of them is stored (a workgroup barrier between the
  *     two), one 16-byte store per unit, no atomics.  Units wholly below the first pad or retired column are not touched;
  *   - m == 0 is allowed: the span becomes 0 and no kernel is launched.  A group with nothing to close (every column
- *     below the tail valid) launches nothing and returns the identity map;
+ *     below the tail valid) launches nothing and returns the identity map; since nothing is written then, bits that
+ *     kwage_group_set_bits planted in the pad columns between the open tail and the span (columns m .. span - 1) are
+ *     NOT zero afterwards: they stay, masked by the valid mask in every reader, until the next live insert overwrites
+ *     everything from column m on;
  *   - flags: KWAGE_SEARCH_TIMING fills stats->kernel_ms with the HIP-event duration of the kernel; other bits are
  *     ignored.  stats may be NULL.
  * Errors, all found before a byte is written -- the matrix, valid mask and span are then as before: KWAGE_ERR_ARG for a

@@ -311,6 +311,7 @@ class Group:
         columns = np.ascontiguousarray(columns, dtype=np.uint64)
         assert rows.shape == columns.shape
         check(lib().kwage_group_set_bits(self._h, rows.ctypes.data, columns.ctypes.data, rows.size))
+        self._column_bits = None                     # (planted bits change the counts: column_bits() is computed afresh)
 
     def read_rows(self, rows: Sequence[int]) -> np.ndarray:
         rows = np.ascontiguousarray(rows, dtype=np.uint32)
@@ -330,7 +331,8 @@ class Group:
 
     def column_bits(self) -> np.ndarray:
         """kwage_group_column_bits(): the set-bit count of every column (uint32 [column_span], 0 on pad columns) -- the
-        denominator of a Jaccard index.  Computed once per group and kept until a live insert or retire changes the group."""
+        denominator of a Jaccard index.  Computed once per group and kept until a live insert, retire, compaction or
+        set_bits changes the group."""
         if self._column_bits is None:
             out = np.zeros(self.column_span, dtype=np.uint32)
             check(lib().kwage_group_column_bits(self._h, out.ctypes.data if out.size else None))

@@ -20,6 +20,9 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN
+# (the expected matrix and the comparisons against it live in tests/group_model.py, which the model-based tests share)
+from group_model import (Image, check_all_forms, check_rows, columns_of, oracle_counts, oracle_hits, random_dna, random_filters,     # noqa: F401
+                         same_state, state_of)
 
 pytestmark = pytest.mark.gpu
 
@@ -46,53 +49,6 @@ def ctx(ka):
 # the numpy side
 # ------------------------------------------------------------------------------------------------------------------
 
-def random_filters(rng, L, n):
-    """uint8 [n, max(1, 2^L / 8)] at density 1/2; for L < 3 the bits at and beyond 2^L are garbage (to be ignored)."""
-    return rng.integers(0, 256, size=(n, max(1, (1 << L) // 8)), dtype=np.uint8)
-
-
-def columns_of(filters, L):
-    """bool [2^L, n]: unpackbits, then the transpose."""
-    return np.unpackbits(filters, axis=1, bitorder="little")[:, :1 << L].T.astype(bool)
-
-
-class Image:
-    """The expected matrix: bool [2^L, span] and the real columns."""
-
-    def __init__(self, L):
-        self.bits = np.zeros((1 << L, 0), dtype=bool)
-        self.real = np.zeros(0, dtype=bool)
-
-    def put(self, first, cols):
-        span = (first + cols.shape[1] + 7) // 8 * 8
-        if span > self.bits.shape[1]:
-            grow = span - self.bits.shape[1]
-            self.bits = np.concatenate([self.bits, np.zeros((self.bits.shape[0], grow), dtype=bool)], axis=1)
-            self.real = np.concatenate([self.real, np.zeros(grow, dtype=bool)])
-        assert not self.real[first:first + cols.shape[1]].any()
-        self.bits[:, first:first + cols.shape[1]] = cols
-        self.real[first:first + cols.shape[1]] = True
-
-    def retire(self, c):
-        assert self.real[c]
-        self.bits[:, c] = False
-        self.real[c] = False
-
-    @property
-    def span(self):
-        return self.bits.shape[1]
-
-    def packed(self):
-        return np.packbits(self.bits, axis=1, bitorder="little")
-
-
-def check_rows(g, image, rows=None):
-    rows = np.arange(image.bits.shape[0]) if rows is None else rows
-    assert g.column_span == image.span and g.row_bytes == image.span // 8 and g.num_columns == int(image.real.sum())
-    got = g.read_rows(rows)
-    assert np.array_equal(got, image.packed()[rows]), np.argwhere(got != image.packed()[rows])[:5]
-
-
 def check_zero_to_the_stride(ka, g, image):
     """(un-finalized groups) One-column blocks behind everything make the rest of the row visible: see the module's text."""
     nrows = image.bits.shape[0]
@@ -106,115 +62,6 @@ def check_zero_to_the_stride(ka, g, image):
     rest = got[:, image.span // 8:]
     assert not rest.any(), (image.span // 8, np.argwhere(rest)[:5])
     return len(wrote)
-
-
-# ------------------------------------------------------------------------------------------------------------------
-# the oracle side: every search form's expected result from the image
-# ------------------------------------------------------------------------------------------------------------------
-
-def oracle_counts(oracle, image, k, nh, L, queries):
-    """(int64 [n, span] num_match of every column, uint32 [n] distinct k-mers)."""
-    packed = np.ascontiguousarray(image.packed())
-    counts = np.zeros((len(queries), image.span), dtype=np.int64)
-    nk = []
-    for q, seq in enumerate(queries):
-        kmers = oracle.unique_kmers(seq, k)
-        nk.append(len(kmers))
-        if len(kmers):
-            for c, m in oracle.search_image(packed, packed.shape[1], k, nh, L, image.span, kmers, 1e-12)[0]:
-                counts[q, c] = m
-    return counts, np.asarray(nk, dtype=np.uint32)
-
-
-def oracle_hits(oracle, image, k, nh, L, queries, t):
-    """[(query, column, num_match)] of the real columns, by (query, column): the oracle's own threshold search."""
-    packed = np.ascontiguousarray(image.packed())
-    out = []
-    for q, seq in enumerate(queries):
-        kmers = oracle.unique_kmers(seq, k)
-        if len(kmers):
-            hits, _ = oracle.search_image(packed, packed.shape[1], k, nh, L, image.span, kmers, float(np.float32(t)))
-            out.extend((q, c, m) for c, m in hits if image.real[c])
-    return out
-
-
-def check_all_forms(ka, oracle, g, image, ctx, k, nh, L, queries, fs_columns, twin=None, topk=5):
-    """Every search form of the group against the oracle on the image (and against `twin`, a group that must answer the
-    same).  Returns the threshold search's records at t = 1 and 0.8 for the caller to compare across states."""
-    from kwage_amd.native import lib
-    counts, nk = oracle_counts(oracle, image, k, nh, L, queries)
-    real = image.real
-    assert np.array_equal(g.real_columns(), real)
-    b = ka.Batch(ctx, queries)
-    kept = {}
-    try:
-        for t in (1.0, 0.8):
-            exp = oracle_hits(oracle, image, k, nh, L, queries, t)
-            for flags in (0, ka.SEARCH_EARLY_EXIT):
-                r = g.search(b, t, flags)
-                got = [tuple(h) for h in r.hits.tolist()]
-                assert np.array_equal(r.num_query_kmer, nk)
-                assert got == exp, (t, flags, got[:5], exp[:5])
-                assert all(real[c] for _, c, _ in got)
-                if twin is not None:
-                    assert [tuple(h) for h in twin.search(b, t, flags).hits.tolist()] == got
-            kept[t] = exp
-            # presence: the same (query, column) pairs as a bitmap
-            floors = np.array([oracle.query_threshold(float(np.float32(t)), int(n)) for n in nk], dtype=np.int64)
-            want = real[None, :] & (counts >= floors[:, None]) & (nk[:, None] > 0)
-            assert {(q, c) for q, c in np.argwhere(want).tolist()} == {(q, c) for q, c, _ in exp}
-            p = g.search_presence(b, t)
-            assert np.array_equal(p.unpack()[:, :image.span], want), t
-            if twin is not None:
-                assert np.array_equal(twin.search_presence(b, t).bits, p.bits)
-        # top-k at floor 0: (score descending, column ascending), cut at k, listed by (query, column)
-        exp_top = []
-        for q in range(len(queries)):
-            if nk[q]:
-                best = sorted((c for c in range(image.span) if real[c]), key=lambda c: (-counts[q, c], c))[:topk]
-                exp_top.extend((q, c, int(counts[q, c])) for c in sorted(best))
-        r = g.search_topk(b, topk)
-        assert [tuple(h) for h in r.hits.tolist()] == exp_top
-        if twin is not None:
-            assert [tuple(h) for h in twin.search_topk(b, topk).hits.tolist()] == exp_top
-        # dense scores
-        want = np.where(real[None, :] & (nk[:, None] > 0), counts, 0).astype(np.uint32)
-        s = g.search_scores(b)
-        assert np.array_equal(s.scores, want)
-        if twin is not None:
-            assert np.array_equal(twin.search_scores(b).scores, want)
-    finally:
-        b.close()
-    # column bits, and the filter search with the listed columns as the questions
-    bits = np.where(real, image.bits.sum(axis=0), 0).astype(np.uint32)
-    assert np.array_equal(g.column_bits(), bits)
-    if fs_columns:
-        fs = ka.FilterSet.from_columns(g, fs_columns)
-        try:
-            shared = np.stack([np.where(real, (image.bits & image.bits[:, c:c + 1]).sum(axis=0), 0) for c in fs_columns]).astype(np.uint32)
-            assert np.array_equal(g.search_filter_scores(fs).scores, shared)
-            assert np.array_equal(fs.bit_counts(), bits[fs_columns])
-            if twin is not None:
-                assert np.array_equal(twin.search_filter_scores(fs).scores, shared)
-        finally:
-            fs.close()
-    for c in np.flatnonzero(~real)[:3].tolist():
-        h = C.c_void_p()
-        cols = np.array([c], dtype=np.uint64)
-        assert lib().kwage_filterset_from_columns(g._h, cols.ctypes.data, 1, C.byref(h)) == ERR_ARG       # a pad column is refused
-    return kept
-
-
-def random_dna(rng, n):
-    return "".join(rng.choice(list("ACGT"), size=n))
-
-
-def state_of(g, nrows):
-    return (g.column_span, g.num_columns, g.row_bytes, g.real_columns().copy(), g.read_rows(np.arange(nrows)) if g.row_bytes else None)
-
-
-def same_state(a, b):
-    return a[:3] == b[:3] and np.array_equal(a[3], b[3]) and (a[4] is None) == (b[4] is None) and (a[4] is None or np.array_equal(a[4], b[4]))
 
 
 # ------------------------------------------------------------------------------------------------------------------
