@@ -272,6 +272,38 @@ typedef struct {
 } kwage_compact_stats;
 int kwage_group_compact(kwage_group *g, uint32_t flags, uint64_t *new_column, uint64_t capacity, kwage_compact_stats *stats);
 
+/* Fold, no counterpart among the reference's programs: a NEW group whose Bloom filters are 2^log_2_filter_len bits long,
+ * made on the device from a resident group with longer ones -- rows per sample is the one size knob of the format, and
+ * this turns it without rebuilding a `.bloom` file.  The reference takes a row index as hash % filter_len with a
+ * power-of-two length (kwage.cpp:411-412, :445), so the filter of a k-mer set at L' = log_2_filter_len is exactly the OR of
+ * the 2^(L - L') consecutive pieces of the same set's filter at L with the same num_hash (how make_bloom_filter itself
+ * shortens a filter, make_bloom.cpp:344-354); in the bit-sliced matrix: dst row r' = OR over j of src row r' + j * 2^L'.
+ *   - *out is a new group on src's context: kmer_len, num_hash and hash_func are src's, log_2_filter_len the argument; row
+ *     stride and column capacity are src's; the matrix comes from kwage_group_create's allocation path, zero-initialised,
+ *     the placement rule applied as there (kwage_group_placement);
+ *   - the column layout is src's, number for number: span, row_bytes, column count, valid mask, and the open tail of a
+ *     live insert.  A column keeps its number; retired and pad columns stay what they were, and bits that
+ *     kwage_group_set_bits planted in pad columns are folded like any others and stay masked;
+ *   - with U = ceil(row_bytes / 16), bytes [0, 16 U) of dst row r' are the OR of the same bytes of src rows
+ *     r' + j * 2^L', j < 2^(L - L'); bytes from 16 U to the stride are zero.  One lane makes one 16-byte unit of one
+ *     destination row from eight loads in flight and one store: one streaming pass, no atomics;
+ *   - src finalized: *out is finalized -- its valid mask uploaded, its bit densities sampled as compact and the live insert
+ *     do; src open: *out is open, and further adds and inserts continue exactly where they would have on src;
+ *   - src, its matrix, mask and state are not changed;
+ *   - 0 <= log_2_filter_len < src's; 0 gives one row;
+ *   - flags: KWAGE_SEARCH_TIMING fills stats->kernel_ms with the HIP-event duration of the kernel; other bits are
+ *     ignored.  stats may be NULL.
+ * Errors, all found before anything is allocated, *out not written: KWAGE_ERR_ARG for a NULL src or out, a sparse group,
+ * log_2_filter_len at or above src's; KWAGE_ERR_STATE while a search is pending on the context.  An allocation that fails
+ * returns kwage_group_create's error with nothing kept.  Synchronous; runs on the context's first stream. */
+typedef struct {
+	uint32_t log_2_before, log_2_after;
+	uint64_t units_per_row;          /* 16-byte units of a row read and written: ceil(row_bytes / 16) */
+	uint64_t bytes_read, bytes_written;
+	float    kernel_ms;              /* with KWAGE_SEARCH_TIMING in flags, else 0 */
+} kwage_fold_stats;
+int kwage_group_fold(kwage_group *src, uint32_t log_2_filter_len, uint32_t flags, kwage_group **out, kwage_fold_stats *stats);
+
 /* ------------------------------------------------------------------------------------
  * Query batch: raw sequences (any case, any characters -- exactly what the reference hands to
  * search(), kwage.cpp:119,137), concatenated, uploaded once and kept resident in HBM.

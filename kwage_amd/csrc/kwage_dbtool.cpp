@@ -18,6 +18,13 @@
 //                                                                   they were built from, <out dir>/<accession>.bloom
 //                                                                   (kwage_group_export_bloom_files), records copied verbatim;
 //                                                                   exit code 1, nothing written, when one is not in the file
+//   kwage_dbtool fold <out.db> <in.db|.dbz> <log2 len>            in.db loaded into a group, its Bloom filters shortened to
+//                                                                   2^<log2 len> bits on the device (kwage_group_fold), all
+//                                                                   columns saved with their records copied verbatim: byte for
+//                                                                   byte what `build` makes of the same filters built at that
+//                                                                   length.  stderr: the share of set bits per column before
+//                                                                   and after and the false-positive rate it buys; exit code 1,
+//                                                                   nothing written, for a length not below the file's
 //   kwage_dbtool mkbloom <out.bloom> <accession> <k> <log2 len|0> <num hash|0> <seq file> [p]
 //                                                                   exact k-mer set of a FASTA/FASTQ -> .bloom; 0 0 = pick the
 //                                                                   parameters with optimal_bloom_param(p, default 0.25)
@@ -25,6 +32,8 @@
 //                                                                   make_bloom_filter() with a minimum k-mer count (reference
 //                                                                   default 5): counting filters sized from the number of bases,
 //                                                                   parameters from optimal_bloom_param; exit code 3 = INVALID
+#include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -52,6 +61,7 @@ static int usage()
 		"       kwage_dbtool append <out.db> <in.db> <x.bloom>...\n"
 		"       kwage_dbtool drop <out.db> <in.db> <run accession>...\n"
 		"       kwage_dbtool extract <out dir> <in.db> [<run accession>...]\n"
+		"       kwage_dbtool fold <out.db> <in.db|.dbz> <log2 len>\n"
 		"       kwage_dbtool mkbloom <out.bloom> <accession> <k> <log2 len|0> <num hash|0> <seq file> [p]\n"
 		"       kwage_dbtool countbloom <out.bloom> <accession> <k> <min count> <seq file>... [-p p] [-l min log2] [-L max log2]\n");
 	return 2;
@@ -171,6 +181,50 @@ static int extract_samples(kwage_ctx *ctx, const char *out_dir, const char *in_d
 	return rc;
 }
 
+// The mean and the largest share of set bits among the columns of a finalized group (kwage_group_column_bits over 2^L rows).
+static int column_shares(kwage_group *g, uint32_t log_2_len, uint32_t num_filter, double *mean, double *largest)
+{
+	std::vector<uint32_t> bits(kwage_group_column_span(g), 0u);
+	if(kwage_group_column_bits(g, bits.data())){ return die("column bits"); }
+	const double rows = (double)(1ull << log_2_len);
+	double sum = 0;
+	uint32_t top = 0;
+	for(uint32_t j = 0; j < num_filter; ++j){ sum += bits[j]; top = std::max(top, bits[j]); }
+	*mean = sum/rows/(double)num_filter;
+	*largest = (double)top/rows;
+	return 0;
+}
+
+static int fold_db(kwage_ctx *ctx, const char *out_db, const char *in_db, uint32_t log_2_len)
+{
+	kwage_db_header h;
+	if(kwage_db_read_header(in_db, &h)){ return die("read header"); }
+	if(log_2_len >= h.log_2_filter_len){
+		fprintf(stderr, "kwage_dbtool: fold: 2^%u is not below the file's filter length 2^%u\n", log_2_len, h.log_2_filter_len);
+		return 1;
+	}
+	kwage_group *g = NULL, *folded = NULL;
+	int rc = load_db(ctx, in_db, 0, &h, &g);
+	if(rc){ return rc; }
+	kwage_fold_stats st;
+	if(kwage_group_fold(g, log_2_len, KWAGE_SEARCH_TIMING, &folded, &st)){ kwage_group_destroy(g); return die("fold"); }
+	std::vector<kwage_save_column> cols;
+	for(uint32_t j = 0; j < h.num_filter; ++j){ cols.push_back(kwage_save_column{j, in_db, j, NULL}); }
+	rc = save_columns(folded, out_db, cols);
+	// what the shorter filters cost: a query k-mer that is absent passes a column with probability share^num_hash
+	double mean[2] = {0, 0}, largest[2] = {0, 0};
+	if(!rc && (kwage_group_finalize(g) || kwage_group_finalize(folded))){ rc = die("finalize"); }
+	if(!rc){ rc = column_shares(g, h.log_2_filter_len, h.num_filter, &mean[0], &largest[0]); }
+	if(!rc){ rc = column_shares(folded, log_2_len, h.num_filter, &mean[1], &largest[1]); }
+	if(!rc){
+		fprintf(stderr, "fold 2^%u -> 2^%u: set bits per column mean %.6f largest %.6f -> mean %.6f largest %.6f, false-positive rate of the largest %.6g -> %.6g, fold kernel %.3f ms\n",
+		        h.log_2_filter_len, log_2_len, mean[0], largest[0], mean[1], largest[1], pow(largest[0], (double)h.num_hash), pow(largest[1], (double)h.num_hash), st.kernel_ms);
+	}
+	kwage_group_destroy(folded);
+	kwage_group_destroy(g);
+	return rc;
+}
+
 int main(int argc, char **argv)
 {
 	if(argc < 3){ return usage(); }
@@ -203,7 +257,7 @@ int main(int argc, char **argv)
 	}
 
 	// the remaining commands run on the device
-	if(cmd != "build" && cmd != "repack" && cmd != "append" && cmd != "drop" && cmd != "extract" && cmd != "mkbloom" && cmd != "countbloom"){ return usage(); }
+	if(cmd != "build" && cmd != "repack" && cmd != "append" && cmd != "drop" && cmd != "extract" && cmd != "fold" && cmd != "mkbloom" && cmd != "countbloom"){ return usage(); }
 	kwage_ctx *ctx = NULL;
 	const char *dev = getenv("KWAGE_DEVICE");
 	if(kwage_init(dev ? atoi(dev) : 0, &ctx)){ return die("init"); }
@@ -227,6 +281,9 @@ int main(int argc, char **argv)
 	}
 	else if(cmd == "extract" && argc >= 4){
 		rc = extract_samples(ctx, argv[2], argv[3], argv + 4, argc - 4);
+	}
+	else if(cmd == "fold" && argc == 5){
+		rc = fold_db(ctx, argv[2], argv[3], (uint32_t)atoi(argv[4]));
 	}
 	else if(cmd == "mkbloom" && argc >= 8){
 		kwage_seqfile *sf = NULL;

@@ -234,6 +234,23 @@ class Group:
         self._column_bits = None
         return new, {f: getattr(st, f) for f, _ in native.CompactStats._fields_}
 
+    def fold(self, log_2_filter_len: int, timing: bool = False) -> Tuple["Group", dict]:
+        """A new group whose Bloom filters are 2^log_2_filter_len bits long (kwage_group_fold): every row of it the OR of the
+        rows of this group that fall on it, made on the device -- bit for bit the group built from the same samples' filters
+        at the short length.  Columns keep their numbers; the new group is finalized if this one is, open otherwise; this
+        group is not changed.  Returns (group, stats)."""
+        h = C.c_void_p()
+        st = native.FoldStats()
+        check(lib().kwage_group_fold(self._h, log_2_filter_len, SEARCH_TIMING if timing else 0, C.byref(h), C.byref(st)))
+        g = Group.__new__(Group)
+        g.ctx = self.ctx
+        g.params = Params(self.params.kmer_len, self.params.num_hash, log_2_filter_len, self.params.hash_func)
+        g._h = h
+        g._nrows = 1 << log_2_filter_len
+        g._real = list(self._real)
+        g._column_bits = None
+        return g, {f: getattr(st, f) for f, _ in native.FoldStats._fields_}
+
     @staticmethod
     def _save_columns(columns: Sequence[int], sources: Sequence):
         """The kwage_save_column array of save_db() and export_bloom_files(): (array, what its entries point to -- to be
@@ -1005,6 +1022,20 @@ class FileDatabase(Database):
             stats.append(st)
         return stats
 
+    def fold(self, log_2_filter_len: int) -> List[dict]:
+        """Shorten the Bloom filters of every resident group whose filters are longer than 2^log_2_filter_len bits to that
+        length (Group.fold): the group is replaced by its fold and closed; groups at or below the length are left alone.
+        Blocks, accessions, live and retired samples stay attached to the same column numbers, so save(), add_sample()
+        (which hashes at the new length), retire_sample(), compact() and every search go on as on any database; two groups
+        that now share their parameters stay two groups.  Returns the stats of the groups folded."""
+        stats = []
+        for gi, g in enumerate(self.groups):
+            if g.params.log_2_filter_len > log_2_filter_len:
+                self.groups[gi], st = g.fold(log_2_filter_len)
+                g.close()
+                stats.append(st)
+        return stats
+
     def save(self, out_dir: str, max_columns: int = 2048) -> List[str]:
         """Write the database as it stands -- live samples included, retired ones left out -- as `.db` files under out_dir
         (Group.save_db): group by group, every sample of _samples() in report order (file samples, then live samples), in
@@ -1015,13 +1046,16 @@ class FileDatabase(Database):
         assert max_columns >= 1
         os.makedirs(out_dir, exist_ok=True)
         written = []
+        parts = {}                                    # (groups that share their parameters after fold(): the numbering goes on)
         for gi, g in enumerate(self.groups):
             mine = [(col, {"run_accession": path.accessions[c]} if isinstance(path, _LiveBlock) else (path, c))
                     for sgi, col, path, c in self._samples() if sgi == gi]
             p = g.params
-            for part, at in enumerate(range(0, len(mine), max_columns)):
+            key = (p.kmer_len, p.log_2_filter_len, p.num_hash, p.hash_func)
+            for at in range(0, len(mine), max_columns):
                 piece = mine[at:at + max_columns]
-                out = os.path.join(out_dir, "k%d_L%d_h%d_f%d_%04d.db" % (p.kmer_len, p.log_2_filter_len, p.num_hash, p.hash_func, part))
+                part = parts[key] = parts.get(key, -1) + 1
+                out = os.path.join(out_dir, "k%d_L%d_h%d_f%d_%04d.db" % (key + (part,)))
                 g.save_db(out, [c for c, _ in piece], [s for _, s in piece])
                 written.append(out)
         return written

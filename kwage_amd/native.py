@@ -90,6 +90,11 @@ class CompactStats(C.Structure):
 NO_COLUMN = 0xFFFFFFFFFFFFFFFF                        # KWAGE_NO_COLUMN
 
 
+class FoldStats(C.Structure):
+    _fields_ = [("log_2_before", C.c_uint32), ("log_2_after", C.c_uint32), ("units_per_row", C.c_uint64),
+                ("bytes_read", C.c_uint64), ("bytes_written", C.c_uint64), ("kernel_ms", C.c_float)]
+
+
 class BloomCounterStats(C.Structure):
     _fields_ = [("num_valid_kmer", C.c_uint64), ("num_bp", C.c_uint64), ("positions", C.c_uint64),
                 ("occurrences_committed", C.c_uint64), ("chunks", C.c_uint64), ("rounds", C.c_uint64),
@@ -156,6 +161,7 @@ _SIGNATURES = [
     ("kwage_group_insert_bloom_files", C.c_int, [_P, C.POINTER(C.c_char_p), C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_float)]),
     ("kwage_group_retire_columns", C.c_int, [_P, _P, C.c_uint64]),
     ("kwage_group_compact", C.c_int, [_P, C.c_uint32, C.POINTER(C.c_uint64), C.c_uint64, C.POINTER(CompactStats)]),
+    ("kwage_group_fold", C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(_P), C.POINTER(FoldStats)]),
     ("kwage_batch_create", C.c_int, [_P, C.c_char_p, _P, C.c_uint32, C.POINTER(_P)]),
     ("kwage_batch_destroy", None, [_P]),
     ("kwage_batch_num_queries", C.c_uint32, [_P]),
