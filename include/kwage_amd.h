@@ -304,6 +304,46 @@ typedef struct {
 } kwage_fold_stats;
 int kwage_group_fold(kwage_group *src, uint32_t log_2_filter_len, uint32_t flags, kwage_group **out, kwage_fold_stats *stats);
 
+/* Copy between groups, no counterpart in the reference: n columns of the resident group src become n new columns of the
+ * resident group dst, packed on the device in one pass over the rows -- how a group grows (everything copied into a wider
+ * one), how groups that share their parameters merge, how a working subset is split off -- without the two transposes and
+ * the host image of kwage_group_export_filters followed by kwage_group_insert_filters.
+ *   - columns[i] is a valid column of src and becomes column *first_column + i of dst: the columns of one call are
+ *     contiguous in dst, in list order.  columns == NULL with n == 0 means every valid column of src, ascending;
+ *   - placement is exactly the live insert's: where dst's last reservation was an insert (or a copy), the call continues at
+ *     the very next column at bit granularity; otherwise it starts at the next 16-byte boundary of the row;
+ *   - after the call dst is bit for bit in the state kwage_group_insert_filters(dst, <those columns exported from src>)
+ *     would have left: the matrix up to the stride, the span, the valid mask, the column count, the open tail, and --
+ *     dst finalized -- finalized still, its bit densities re-sampled.  Bits of the first word below *first_column are kept
+ *     from memory; bits at and above the new tail are written as zero, to the end of the last 32-bit word the call
+ *     touches -- what the insert owns; bits that kwage_group_set_bits planted between an open tail and the span are
+ *     overwritten;
+ *   - src, its matrix, mask and state are not changed; bits in pad or retired columns of src never travel: a listed
+ *     column's neighbours in a source word are masked out;
+ *   - one lane makes one 16-byte unit of one destination row and stores it once; dst is read only by the owner of a
+ *     row's first unit (where *first_column is no multiple of 128, for the bits below it) and of its last unit (where the
+ *     last word written is not the unit's last, for the words above it).  No atomics;
+ *   - before and after kwage_group_finalize, on either group, independently;
+ *   - flags: KWAGE_SEARCH_TIMING fills stats->kernel_ms with the HIP-event duration of the kernel; other bits are
+ *     ignored.  stats may be NULL.
+ * Errors, all found before a byte is written or allocated -- *first_column and *stats are not written, dst is as before --
+ * in this order: KWAGE_ERR_ARG for a NULL dst, src or first_column; columns == NULL with n != 0, or columns != NULL with
+ * n == 0; dst == src; groups of different contexts; a sparse group on either side; kmer_len, num_hash, log_2_filter_len
+ * or hash_func differing; then KWAGE_ERR_STATE while a search is pending on the context; then KWAGE_ERR_ARG again for a
+ * src without valid columns in the all-columns form; n > 2^32 - 1; a column at or beyond src's span, a pad or retired
+ * column, a column listed twice (the first offender in list order); more columns than dst's capacity holds
+ * (*first_column + n > 8 * row_stride).  Synchronous; runs on the context's first stream. */
+typedef struct {
+	uint64_t first_column;            /* where columns[0] went in dst                                   */
+	uint64_t columns;                 /* n copied                                                       */
+	uint64_t runs;                    /* stretches of consecutive source columns the list folded into   */
+	uint64_t first_unit, units;       /* 16-byte units of a dst row written: [first_unit, first_unit+units) */
+	uint64_t bytes_written;           /* rows * units * 16                                              */
+	float    kernel_ms;               /* with KWAGE_SEARCH_TIMING in flags, else 0                      */
+} kwage_copy_stats;
+int kwage_group_copy_columns(kwage_group *dst, kwage_group *src, const uint64_t *columns, uint64_t n,
+                             uint32_t flags, uint64_t *first_column, kwage_copy_stats *stats);
+
 /* ------------------------------------------------------------------------------------
  * Query batch: raw sequences (any case, any characters -- exactly what the reference hands to
  * search(), kwage.cpp:119,137), concatenated, uploaded once and kept resident in HBM.

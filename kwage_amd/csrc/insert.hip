@@ -25,6 +25,8 @@ using namespace kwage;
 
 // loader.hip
 namespace kwage { void group_probe_density(kwage_group *g); }
+// (defined below; copy.hip calls it too)
+namespace kwage { int commit_insert(kwage_group *g, uint64_t first, uint64_t n); }
 
 namespace {
 
@@ -50,8 +52,11 @@ hipError_t launch_insert(const uint8_t *d_in, uint64_t in_stride, uint32_t n, ui
 	return hipGetLastError();
 }
 
-// The columns first .. first + n - 1 are in the matrix: the group's state follows.
-int commit_insert(kwage_group *g, uint64_t first, uint64_t n)
+}  // namespace
+
+// The columns first .. first + n - 1 are in the matrix: the group's state follows.  (Shared with the copy between groups,
+// copy.hip, whose columns arrive exactly as an insert's do.)
+int kwage::commit_insert(kwage_group *g, uint64_t first, uint64_t n)
 {
 	kwage_ctx *ctx = g->ctx;
 	for(uint64_t c = first; c < first + n; ++c){ g->h_valid[c/8] |= (uint8_t)(1u << (c%8)); }
@@ -65,6 +70,8 @@ int commit_insert(kwage_group *g, uint64_t first, uint64_t n)
 	HIP_TRY(hipStreamSynchronize(ctx->stream));
 	return KWAGE_OK;
 }
+
+namespace {
 
 struct Events {
 	hipEvent_t ev0 = nullptr, ev1 = nullptr;

@@ -60,8 +60,9 @@ KWAGE_HD inline uint32_t save_find_run(const SaveRun *runs, uint32_t n_runs, uin
 	return lo;
 }
 
-// Destination bits [d0, d1) of one row (d0 a multiple of 32, d1 - d0 <= 32, d1 <= n) as a word, bit d - d0 = destination
-// column d; *k = the run that covers d0 on entry and the one that covers d1 (if any) on return.  The kernel's inner loop.
+// Destination bits [d0, d1) of one row (d1 - d0 <= 32, d1 <= n; d0 a multiple of 32 in the save and the compaction, any
+// column in the copy between groups) as a word, bit d - d0 = destination column d; *k = the run that covers d0 on entry
+// and the one that covers d1 (if any) on return.  The kernel's inner loop.
 template <typename LOAD>
 KWAGE_HD inline uint32_t save_word(LOAD &&load, const SaveRun *runs, uint32_t *k, uint64_t row, uint64_t stride, uint64_t matrix_bytes, uint32_t d0, uint32_t d1)
 {
@@ -101,12 +102,10 @@ KWAGE_HD inline void save_unit_in_run(LOAD &&load, LOAD4 &&load4, uint64_t row, 
 // The column list of a save folded into runs, in list order: destination column i is source column columns[i].  Refused
 // (KWAGE_ERR_ARG, `runs` empty): n == 0 or n > 2^32 - 1 (num_filter is a uint32_t), a column at or beyond the span, a
 // pad or retired column of valid[] (the group's host valid mask, a bit per column, LSB first), a column named twice.
-inline int plan_save(const uint64_t *columns, uint64_t n, uint64_t span, const uint8_t *valid, std::vector<SaveRun> &runs)
+// The column checks and the folding are shared with the copy between groups (copy_plan.hpp plan_copy), which names itself
+// in `who`.
+inline int save_check_columns(const char *who, const uint64_t *columns, uint64_t n, uint64_t span, const uint8_t *valid)
 {
-	const char *who = "kwage_group_save_db";
-	runs.clear();
-	if(n == 0){ return fail(KWAGE_ERR_ARG, "%s: n is 0", who); }
-	if(n > 0xFFFFFFFFull){ return fail(KWAGE_ERR_ARG, "%s: %llu columns do not fit num_filter", who, (unsigned long long)n); }
 	std::vector<uint8_t> seen((span + 7)/8, 0);
 	for(uint64_t i = 0; i < n; ++i){
 		const uint64_t c = columns[i];
@@ -115,10 +114,25 @@ inline int plan_save(const uint64_t *columns, uint64_t n, uint64_t span, const u
 		if((seen[c/8] >> (c%8)) & 1){ return fail(KWAGE_ERR_ARG, "%s: column %llu is listed twice", who, (unsigned long long)c); }
 		seen[c/8] |= (uint8_t)(1u << (c%8));
 	}
+	return KWAGE_OK;
+}
+inline void save_fold_runs(const uint64_t *columns, uint64_t n, std::vector<SaveRun> &runs)
+{
+	runs.clear();
 	for(uint64_t i = 0; i < n; ++i){
 		if(!runs.empty() && columns[i] == runs.back().src_first + runs.back().len){ ++runs.back().len; }
 		else{ runs.push_back(SaveRun{columns[i], (uint32_t)i, 1u}); }
 	}
+}
+inline int plan_save(const uint64_t *columns, uint64_t n, uint64_t span, const uint8_t *valid, std::vector<SaveRun> &runs)
+{
+	const char *who = "kwage_group_save_db";
+	runs.clear();
+	if(n == 0){ return fail(KWAGE_ERR_ARG, "%s: n is 0", who); }
+	if(n > 0xFFFFFFFFull){ return fail(KWAGE_ERR_ARG, "%s: %llu columns do not fit num_filter", who, (unsigned long long)n); }
+	const int rc = save_check_columns(who, columns, n, span, valid);
+	if(rc){ return rc; }
+	save_fold_runs(columns, n, runs);
 	return KWAGE_OK;
 }
 

@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import ctypes as C
 from dataclasses import dataclass
-from typing import List, Sequence, Tuple
+from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -114,6 +114,7 @@ class Group:
         self._nrows = 1 << log_2_filter_len          # rows an add_columns() image must hold
         self._real: List[Tuple[int, int]] = []       # (first column, columns) of everything added: the rest of the span is padding
         self._column_bits = None                     # column_bits(), once computed
+        self._tail = None                            # the open tail a live insert left (the next insert's column), None while closed
         check(lib().kwage_group_create(ctx._h, C.byref(self.params), column_capacity, C.byref(self._h)))
 
     @classmethod
@@ -129,6 +130,7 @@ class Group:
         g._nrows = int(rows.size)                     # a sparse group's images hold the listed rows only
         g._real = []
         g._column_bits = None
+        g._tail = None
         check(lib().kwage_group_create_sparse(ctx._h, C.byref(g.params), column_capacity, rows.ctypes.data, rows.size, C.byref(g._h)))
         return g
 
@@ -145,12 +147,14 @@ class Group:
         first = C.c_uint64()
         check(lib().kwage_group_add_columns(self._h, rows.ctypes.data, rows.strides[0], num_filter, C.byref(first)))
         self._real.append((first.value, num_filter))
+        self._tail = None
         return first.value
 
     def add_db_file(self, path: str) -> Tuple[int, int]:
         first, nf = C.c_uint64(), C.c_uint32()
         check(lib().kwage_group_add_db_file(self._h, path.encode(), C.byref(first), C.byref(nf)))
         self._real.append((first.value, nf.value))
+        self._tail = None
         return first.value, nf.value
 
     def add_db_files(self, paths: Sequence[str]) -> List[Tuple[int, int]]:
@@ -160,16 +164,19 @@ class Group:
         first, nf = (C.c_uint64 * n)(), (C.c_uint32 * n)()
         check(lib().kwage_group_add_db_files(self._h, arr, n, first, nf))
         self._real.extend((int(first[i]), int(nf[i])) for i in range(n))
+        self._tail = None
         return [(int(first[i]), int(nf[i])) for i in range(n)]
 
     def add_random_columns(self, num_columns: int, seed: int, density_q8: int) -> int:
         first = C.c_uint64()
         check(lib().kwage_group_add_random_columns(self._h, num_columns, seed, density_q8, C.byref(first)))
         self._real.append((first.value, num_columns))
+        self._tail = None
         return first.value
 
     def _inserted(self, first: int, n: int) -> int:
         self._real.append((first, n))
+        self._tail = first + n
         self._column_bits = None                     # (a live group changes: column_bits() is computed afresh)
         return first
 
@@ -231,6 +238,7 @@ class Group:
         check(lib().kwage_group_compact(self._h, SEARCH_TIMING if timing else 0, new.ctypes.data_as(C.POINTER(C.c_uint64)), span, C.byref(st)))
         new = new[:span].view(np.int64)              # (KWAGE_NO_COLUMN is -1 as int64)
         self._real = [(0, int(st.columns))] if st.columns else []
+        self._tail = int(st.columns)
         self._column_bits = None
         return new, {f: getattr(st, f) for f, _ in native.CompactStats._fields_}
 
@@ -249,7 +257,24 @@ class Group:
         g._nrows = 1 << log_2_filter_len
         g._real = list(self._real)
         g._column_bits = None
+        g._tail = self._tail
         return g, {f: getattr(st, f) for f, _ in native.FoldStats._fields_}
+
+    def copy_columns_from(self, src: "Group", cols: Optional[Sequence[int]] = None, timing: bool = False) -> Tuple[int, dict]:
+        """Columns of another resident group become new columns of this one, packed on the device
+        (kwage_group_copy_columns): cols[i] of `src` becomes column first_column + i, placed as insert_filters() places its
+        filters; cols=None takes every valid column of `src`, ascending.  This group is afterwards bit for bit what
+        insert_filters(src.export_filters(cols)) would have made of it; `src` is not changed.  Returns (first_column, stats)."""
+        first = C.c_uint64()
+        st = native.CopyStats()
+        if cols is None:
+            ptr, n = None, 0
+        else:
+            cols = np.ascontiguousarray(cols, dtype=np.uint64)
+            ptr, n = cols.ctypes.data_as(C.c_void_p), cols.size      # (an empty list is refused: the pointer is not NULL)
+        check(lib().kwage_group_copy_columns(self._h, src._h, ptr, n, SEARCH_TIMING if timing else 0, C.byref(first), C.byref(st)))
+        self._inserted(first.value, int(st.columns))
+        return first.value, {f: getattr(st, f) for f, _ in native.CopyStats._fields_}
 
     @staticmethod
     def _save_columns(columns: Sequence[int], sources: Sequence):
@@ -355,6 +380,12 @@ class Group:
             check(lib().kwage_group_column_bits(self._h, out.ctypes.data if out.size else None))
             self._column_bits = out
         return self._column_bits
+
+    @property
+    def room(self) -> int:
+        """Columns a live insert (or copy_columns_from) could still take: the row's capacity behind where it would land."""
+        landing = self._tail if self._tail is not None else (self.row_bytes + 15) // 16 * 16 * 8
+        return max(0, 8 * self.row_stride - landing)
 
     num_columns = property(lambda self: lib().kwage_group_num_columns(self._h))
     column_span = property(lambda self: lib().kwage_group_column_span(self._h))
@@ -911,7 +942,9 @@ class FileDatabase(Database):
     grouped by (kmer_len, num_hash, log_2_filter_len, hash_func), each group one HBM matrix; hits are
     mapped back to (file, column) and carry the sample's run accession.  With headroom > 0 every group has room for
     that many more columns: add_sample() makes new samples searchable in the resident groups (live insert),
-    retire_sample() withdraws one, compact() gives the withdrawn samples' columns back to add_sample()."""
+    retire_sample() withdraws one, compact() gives the withdrawn samples' columns back to add_sample(), reserve() makes
+    room again once the headroom is used up (a wider group, the columns copied on the device), merge_groups() makes one
+    group of those that share their parameters."""
 
     def __init__(self, ctx: Context, paths: Sequence[str], headroom: int = 0):
         import os
@@ -1008,26 +1041,114 @@ class FileDatabase(Database):
         stats = []
         for gi, g in enumerate(self.groups):
             new, st = g.compact()
-            layout = []
-            for first, nf, path, f0 in self._layout[gi]:
-                kept = [c for c in range(nf) if new[first + c] >= 0]
-                for i, c in enumerate(kept):
-                    if i and kept[i - 1] == c - 1:
-                        at, n, p, f = layout[-1]
-                        layout[-1] = (at, n + 1, p, f)
-                    else:
-                        layout.append((int(new[first + c]), 1, path, f0 + c))
-            self._layout[gi] = layout
+            self._layout[gi] = self._renumbered(gi, new)
             self._retired = {(g2, c) for g2, c in self._retired if g2 != gi}
             stats.append(st)
         return stats
+
+    def _renumbered(self, gi: int, new) -> list:
+        """The layout of group gi after its columns moved: new[c] is column c's new number, negative for a column that is
+        gone (a pad or retired column).  A block cut by a column that is gone becomes two pieces."""
+        layout = []
+        for first, nf, path, f0 in self._layout[gi]:
+            kept = [c for c in range(nf) if new[first + c] >= 0]
+            for i, c in enumerate(kept):
+                if i and kept[i - 1] == c - 1:
+                    at, n, p, f = layout[-1]
+                    layout[-1] = (at, n + 1, p, f)
+                else:
+                    layout.append((int(new[first + c]), 1, path, f0 + c))
+        return layout
+
+    def _copied_into(self, dst: Group, gi: int) -> Tuple[list, dict]:
+        """The valid columns of group gi copied, ascending, behind what `dst` holds (Group.copy_columns_from): (the
+        group's layout under the new column numbers, the copy's stats -- {} for a group without columns)."""
+        g = self.groups[gi]
+        cols = np.flatnonzero(g.real_columns())
+        new = np.full(max(g.column_span, 1), -1, dtype=np.int64)
+        st = {}
+        if cols.size:
+            first, st = dst.copy_columns_from(g, cols)
+            new[cols] = first + np.arange(cols.size)
+        return self._renumbered(gi, new), st
+
+    def reserve(self, headroom: int) -> List[dict]:
+        """Room for `headroom` more add_sample() calls in every group, without a save and a reload: a group in which fewer
+        columns fit behind where the next insert would land (Group.room) is replaced by a NEW group of its valid columns
+        rounded up to 128, plus headroom, columns -- all valid columns copied on the device, ascending
+        (Group.copy_columns_from), the new group finalized, the old one closed.  Columns are renumbered as compact()
+        renumbers them, and every method answers as before.  An allocation that fails leaves the old group in place and
+        raises.  Returns the stats of the copies made."""
+        stats = []
+        for gi, g in enumerate(self.groups):
+            if g.room >= headroom:
+                continue
+            p = g.params
+            wide = Group(self.ctx, p.kmer_len, p.num_hash, p.log_2_filter_len, (g.num_columns + 127) // 128 * 128 + headroom, p.hash_func)
+            try:
+                layout, st = self._copied_into(wide, gi)
+                wide.finalize()
+            except Exception:
+                wide.close()
+                raise
+            self.groups[gi], self._layout[gi] = wide, layout
+            self._retired = {(g2, c) for g2, c in self._retired if g2 != gi}
+            g.close()
+            stats.append(st)
+        return stats
+
+    def merge_groups(self) -> int:
+        """Groups that share kmer_len, num_hash, log_2_filter_len and hash_func -- after fold(), or where the database was
+        put together from several -- become ONE new group whose capacity is the sum of theirs: their valid columns copied
+        on the device in group order (Group.copy_columns_from), the new group finalized, the old ones closed.  The new
+        group takes the place of the first of them; layout entries and live blocks are re-attached under the new group
+        index and column numbers (retired columns do not travel), so the report order of _blocks() stays: files in file
+        order, then the live blocks group by group -- a merged group's at the place of its first member.  From then on a
+        search runs once for them and save() writes one numbering.  Returns the number of groups removed."""
+        members = {}
+        for gi, g in enumerate(self.groups):
+            p = g.params
+            members.setdefault((p.kmer_len, p.num_hash, p.log_2_filter_len, p.hash_func), []).append(gi)
+        merged = {}                                   # first member's index -> (new group, its layout)
+        for (k, nh, lg, hf), gis in members.items():
+            if len(gis) < 2:
+                continue
+            one = Group(self.ctx, k, nh, lg, sum(8 * self.groups[gi].row_stride for gi in gis), hf)
+            try:
+                layout = [e for gi in gis for e in self._copied_into(one, gi)[0]]
+                one.finalize()
+            except Exception:
+                one.close()
+                for g, _ in merged.values():
+                    g.close()
+                raise
+            merged[gis[0]] = (one, layout)
+        gone = {gi for gis in members.values() if len(gis) > 1 for gi in gis}
+        groups, layouts, index = [], [], {}
+        for gi, g in enumerate(self.groups):
+            if gi in merged:
+                g, layout = merged[gi]
+            elif gi in gone:
+                continue
+            else:
+                layout = self._layout[gi]
+            index[gi] = len(groups)
+            groups.append(g)
+            layouts.append(layout)
+        for gi in gone:
+            self.groups[gi].close()
+        removed = len(self.groups) - len(groups)
+        self._retired = {(index[gi], c) for gi, c in self._retired if gi not in gone}
+        self.groups, self._layout = groups, layouts
+        return removed
 
     def fold(self, log_2_filter_len: int) -> List[dict]:
         """Shorten the Bloom filters of every resident group whose filters are longer than 2^log_2_filter_len bits to that
         length (Group.fold): the group is replaced by its fold and closed; groups at or below the length are left alone.
         Blocks, accessions, live and retired samples stay attached to the same column numbers, so save(), add_sample()
         (which hashes at the new length), retire_sample(), compact() and every search go on as on any database; two groups
-        that now share their parameters stay two groups.  Returns the stats of the groups folded."""
+        that now share their parameters stay two groups until merge_groups() makes them one.  Returns the stats of the
+        groups folded."""
         stats = []
         for gi, g in enumerate(self.groups):
             if g.params.log_2_filter_len > log_2_filter_len:
