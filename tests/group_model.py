@@ -5,9 +5,11 @@ oracle helpers that compare a device group with an expected matrix.
   GroupModel      the state: every bit of every row up to the row stride, the valid mask, next_byte, the tail, finalized.
                   One method per mutator (add_columns, insert, retire, set_bits, compact, finalize); each returns what the C
                   ABI call must return -- the first column, (column map, stats), 0 -- or the error code, the state then
-                  untouched.  The rules are restated from the header's text; none of the planners (insert_plan.hpp,
-                  compact_plan.hpp) is called: tests/test_group_model.py compares the two, tests/test_gpu_group_model.py
-                  replays the sequences on the device and compares after every step.
+                  untouched.  fold(L2) returns (a NEW model, the stats of kwage_group_fold) and leaves this one alone
+                  (tests/family_model.py walks over several models).  The rules are restated from the header's text; none
+                  of the planners (insert_plan.hpp, compact_plan.hpp, fold_plan.hpp) is called: tests/test_group_model.py
+                  and tests/test_family_model.py compare the two, tests/test_gpu_group_model.py and
+                  tests/test_gpu_family_model.py replay the sequences on the device and compare after every step.
   sequence        (seed, shape) -> Sequence: about 45 operations of a seeded walk on the model, the planned refusals and the
                   checkpoints (where the GPU test runs every search form) included, and the seed's queries.
   Image, check_rows, check_all_forms, oracle_counts, oracle_hits, state_of, same_state ...
@@ -312,6 +314,24 @@ class GroupModel:
     def finalize(self):
         self.finalized = True
         return 0
+
+    # -- kwage_group_fold: a NEW group of 2^L2 rows at the same stride; with U = ceil(row_bytes / 16), bytes [0, 16 U) of
+    #    row r' are the OR of the same bytes of the rows r' + j * 2^L2, everything from 16 U to the stride is zero; the
+    #    column layout (valid mask, next_byte, the tail) and finalized are this group's, which is not changed
+    def fold(self, L2):
+        if not 0 <= L2 < self.L:
+            return ERR_ARG
+        units = (self.next_byte + 15) // 16
+        m = GroupModel(L2, self.stride)
+        m.matrix[:, :128 * units] = self.matrix[:, :128 * units].reshape(1 << (self.L - L2), 1 << L2, 128 * units).any(axis=0)
+        m.valid = self.valid.copy()
+        m.next_byte, m.tail_open, m.tail_column, m.finalized = self.next_byte, self.tail_open, self.tail_column, self.finalized
+        return m, {"log_2_before": self.L, "log_2_after": L2, "units_per_row": units, "bytes_read": 16 * units << self.L,
+                   "bytes_written": 16 * units << L2}
+
+    def room(self):
+        """Columns a live insert (or a copy) could still take."""
+        return 8 * self.stride - (self.tail_column if self.tail_open else (self.next_byte + 15) // 16 * 16 * 8)
 
     def apply(self, op):
         """One Op of a sequence on this model -> what the call returns."""

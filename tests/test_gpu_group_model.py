@@ -25,6 +25,13 @@ column_bits comparison of the checkpoint behind a retire fails, and with commit_
 t = 1 hit list of the next checkpoint lacks the inserted columns -- each in all nine finalizing seeds; FileDatabase.compact
 keeping its set of retired file columns fails test_file_database_sequences at seeds 1 and 3.
 
+test_file_database_sequences also holds FileDatabase.fold, reserve and merge_groups (and a live sample added under a file
+sample's accession), shuffled in with the older steps on a directory built for it: three files that share (k, num_hash,
+hash_func) at L = 12, 10, 10 and one at other parameters BEHIND them, so that a merge moves its group's index.  Its
+DatabaseModel is a list of groups in db.groups order, every sample knowing where it came from; the report order is restated
+from the doc-strings of _blocks and merge_groups.  On an MI355X all four seeds answer as the model says; merge_groups not
+re-indexing _retired (a local mutation) fails all four in the check behind the merge.
+
 Wall time on one MI355X, the whole -m gpu suite with each file in its own process: 953 s with this file, 934 s for the
 files the parent commit has (the same run; a process start, torch's import included, is about 11 s of every file's time);
 this file 19 s in its own process (17 s inside pytest, 11 s of them the first test's imports): no sequence takes more
@@ -36,8 +43,6 @@ from collections import Counter
 
 import numpy as np
 import pytest
-
-from conftest import GOLDEN
 
 import compact_cases as cc
 import group_model as gm
@@ -213,62 +218,99 @@ def test_a_truncated_walk_ran():
 # ----------------------------------------------------------------------------------------------------------------------
 
 class DatabaseModel:
-    """Run accession -> bool column, per parameter set, in the order a FileDatabase reports samples: the files' samples in
-    file order, then the live samples group by group.  Built from the files with the oracle's reader."""
+    """The groups of a FileDatabase in db.groups order: each its parameters and its samples in COLUMN order, a sample
+    being (where it came from, run accession, bool column) -- it came from (0, file index, column in the file) or, added
+    live, from (1, serial number).  Built from the files with the oracle's reader, as FileDatabase groups them: by
+    parameters, sorted, a group's files in file order.
+
+    The report order is restated from the doc-strings of FileDatabase._blocks and merge_groups: the files' samples in
+    file order (a file's in column order), then the live samples group by group in column order; a merged group stands at
+    the place of its first member and holds its members' samples in member order."""
 
     def __init__(self, oracle, files):
-        self.oracle = oracle
-        self.files_samples, self.live = [], {}            # [(key, accession, column)]; key -> [(accession, column)]
-        for f in files:
+        self.oracle, self.n_live = oracle, 0
+        by = {}
+        for fi, f in enumerate(files):
             d = oracle.read_db(f)
             h = d.header
             cols = np.unpackbits(np.ascontiguousarray(d.rows), axis=1, bitorder="little")[:, :h.num_filter].astype(bool)
             for j in range(h.num_filter):
-                self.files_samples.append(((h.kmer_len, h.num_hash, h.log_2_filter_len, h.hash_func), d.info(j).csv_string(), cols[:, j].copy()))
+                by.setdefault((h.kmer_len, h.num_hash, h.log_2_filter_len, h.hash_func), []).append(((0, fi, j), d.info(j).csv_string(), cols[:, j].copy()))
+        self.groups = [[key, samples] for key, samples in sorted(by.items())]        # [parameters, [(origin, accession, column)]]
 
     def keys(self):
-        return sorted({s[0] for s in self.files_samples} | {key for key, lst in self.live.items() if lst})
+        return [key for key, _ in self.groups]
 
     def report(self):
-        return self.files_samples + [(key, a, c) for key in self.keys() for a, c in self.live.get(key, [])]
+        """[(parameters, accession, column, group index, origin)] in report order."""
+        everything = [(key, a, c, gi, origin) for gi, (key, samples) in enumerate(self.groups) for origin, a, c in samples]
+        return sorted((s for s in everything if s[4][0] == 0), key=lambda s: s[4]) + [s for s in everything if s[4][0] == 1]
 
-    def group(self, key):
-        """The samples of one group in column order."""
-        return [s for s in self.files_samples if s[0] == key] + [(key, a, c) for a, c in self.live.get(key, [])]
+    def group(self, gi):
+        """The samples of one group in column order, as report() lists them."""
+        key, samples = self.groups[gi]
+        return [(key, a, c, gi, origin) for origin, a, c in samples]
 
-    def add(self, key, accession, seq):
-        k, nh, L, _ = key
+    def live(self):
+        return [s[1] for s in self.report() if s[4][0] == 1]
+
+    def add(self, gi, accession, seq):
+        """A live sample: its filter built at the length the group has NOW, its column behind every other of the group."""
+        k, nh, L, _ = self.groups[gi][0]
         bits = self.oracle.bloom_bits_from_sequences([seq], k, nh, L)
-        self.live.setdefault(key, []).append((accession, gm.columns_of(bits[None, :], L)[:, 0]))
+        self.groups[gi][1].append(((1, self.n_live), accession, gm.columns_of(bits[None, :], L)[:, 0]))
+        self.n_live += 1
 
     def retire(self, accession):
-        for i, s in enumerate(self.files_samples):
-            if s[1] == accession:
-                del self.files_samples[i]
-                return
-        for lst in self.live.values():
-            for i, s in enumerate(lst):
-                if s[0] == accession:
-                    del lst[i]
-                    return
+        """The first sample in report order carrying the accession is withdrawn -> (group index, where it came from)."""
+        for key, a, c, gi, origin in self.report():
+            if a == accession:
+                self.groups[gi][1][:] = [s for s in self.groups[gi][1] if s[0] != origin]
+                return gi, origin
         raise KeyError(accession)
 
+    def fold(self, L2):
+        """Every group with longer filters: its columns folded by GroupModel's rule, row r' the OR of rows r' + j * 2^L2.
+        -> the group indices folded."""
+        done = []
+        for gi, (key, samples) in enumerate(self.groups):
+            k, nh, L, hf = key
+            if L > L2:
+                self.groups[gi] = [(k, nh, L2, hf), [(origin, a, c.reshape(1 << (L - L2), 1 << L2).any(axis=0)) for origin, a, c in samples]]
+                done.append(gi)
+        return done
+
+    def merge(self):
+        """Groups that share their parameters become one at the place of the first -> [member indices] of every group of
+        the new list."""
+        members = {}
+        for gi, (key, _) in enumerate(self.groups):
+            members.setdefault(key, []).append(gi)
+        groups, made = [], []
+        for gi, (key, _) in enumerate(self.groups):
+            if members[key][0] == gi:
+                groups.append([key, [s for g2 in members[key] for s in self.groups[g2][1]]])
+                made.append(members[key])
+        self.groups = groups
+        return made
+
     def contents(self):
-        return Counter((key, a, c.tobytes()) for key, a, c in self.report())
+        return Counter((key, a, c.tobytes()) for key, a, c, _, _ in self.report())
 
     def counts(self, queries):
-        """(int64 [n queries, n samples] in report order, {key: per query distinct k-mers})."""
+        """(int64 [n queries, n samples] in report order, {parameters: per query distinct k-mers})."""
         report = self.report()
         out = np.zeros((len(queries), len(report)), dtype=np.int64)
         nks = {}
-        for key in self.keys():
+        for gi, (key, samples) in enumerate(self.groups):
             k, nh, L, _ = key
-            idx = [i for i, s in enumerate(report) if s[0] == key]
+            nks[key] = [len(self.oracle.unique_kmers(seq, k)) for seq in queries]
+            idx = [i for i, s in enumerate(report) if s[3] == gi]
+            if not idx:
+                continue
             packed = np.ascontiguousarray(np.packbits(np.stack([report[i][2] for i in idx], axis=1), axis=1, bitorder="little"))
-            nks[key] = []
             for q, seq in enumerate(queries):
                 kmers = self.oracle.unique_kmers(seq, k)
-                nks[key].append(len(kmers))
                 if len(kmers):
                     for c, m in self.oracle.search_image(packed, packed.shape[1], k, nh, L, len(idx), kmers, 1e-12)[0]:
                         out[q, idx[c]] = m
@@ -277,15 +319,16 @@ class DatabaseModel:
     def hits(self, queries, t):
         """Counter of (query, accession, found, distinct k-mers): the oracle's own threshold search, group by group."""
         out = Counter()
-        for key in self.keys():
+        for gi, (key, samples) in enumerate(self.groups):
             k, nh, L, _ = key
-            mine = self.group(key)
-            packed = np.ascontiguousarray(np.packbits(np.stack([s[2] for s in mine], axis=1), axis=1, bitorder="little"))
+            if not samples:
+                continue
+            packed = np.ascontiguousarray(np.packbits(np.stack([s[2] for s in samples], axis=1), axis=1, bitorder="little"))
             for q, seq in enumerate(queries):
                 kmers = self.oracle.unique_kmers(seq, k)
                 if len(kmers):
-                    for c, m in self.oracle.search_image(packed, packed.shape[1], k, nh, L, len(mine), kmers, float(np.float32(t)))[0]:
-                        out[(q, mine[c][1], m, len(kmers))] += 1
+                    for c, m in self.oracle.search_image(packed, packed.shape[1], k, nh, L, len(samples), kmers, float(np.float32(t)))[0]:
+                        out[(q, samples[c][1], m, len(kmers))] += 1
         return out
 
 
@@ -301,47 +344,130 @@ def check_database(db, model, queries):
     counts, _ = model.counts(queries)
     assert np.array_equal(scores, counts.astype(np.uint32))
     assert sum(g.num_columns for g in db.groups) == len(report)
+    assert [g.num_columns for g in db.groups] == [len(samples) for _, samples in model.groups]
+
+
+DB_FILES = [("a.db", (21, 2, 12), range(0, 5)), ("b.db", (21, 2, 10), range(5, 9)), ("c.db", (21, 2, 10), range(9, 12)),
+            ("d.db", (25, 2, 11), range(12, 16))]          # (d.db: the group BEHIND those a fold makes equal -- a merge moves its index)
+
+
+def build_directory(ctx, oracle, tmp_path, seqs):
+    """`.db` files under tmp_path/src from oracle-built `.bloom` files: three that share (k, num_hash, hash_func) at
+    L = 12, 10, 10 and one at other parameters; sample i is SRR<8300 + i>."""
+    import ctypes as C
+    from kwage_amd.native import lib, check, Params
+    src = tmp_path / "src"
+    src.mkdir()
+    for name, (k, nh, lg), members in DB_FILES:
+        paths = []
+        for i in members:
+            p = str(tmp_path / ("SRR%d_L%d.bloom" % (8300 + i, lg)))
+            oracle.write_bloom(p, k, lg, nh, oracle.FilterInfo(run_accession=oracle.str_to_accession("SRR%d" % (8300 + i))),
+                               oracle.bloom_bits_from_sequences([seqs[i]], k, nh, lg))
+            paths.append(p)
+        prm = Params(k, nh, lg, 0)
+        arr = (C.c_char_p * len(paths))(*[p.encode() for p in paths])
+        check(lib().kwage_build_db(ctx._h, str(src / name).encode(), C.byref(prm), arr, len(paths), None))
+    return str(src)
+
+
+def database_plan(rng, seed):
+    """The steps of a seed: the old kinds and fold, merge, reserve, add_dup shuffled together, under the order every seed
+    keeps -- a retire_file before the fold, the fold before the merge (a retire in the LAST group between them, nothing
+    compacted: the merge has a retired file column to re-index), and a retire, a compact and a save_reopen behind the merge.
+    Seed 1 reserves between the fold and the merge, the others behind the merge."""
+    first = ["add", "add", "retire_file", "compact", "add_dup", "export"]
+    between = ["add", "retire_dup", "retire_last_group"] + (["reserve"] if seed == 1 else [])
+    after = ["retire_live", "retire_file", "compact", "save_reopen", "add", "retire_dup2", "export"] + ([] if seed == 1 else ["reserve"])
+    for part in (first, between, after):
+        rng.shuffle(part)
+    return first + ["fold"] + between + ["merge"] + after
 
 
 @pytest.mark.parametrize("seed", range(4))
 def test_file_database_sequences(ka, ctx, oracle, tmp_path, seed):
     rng = np.random.default_rng(7000 + seed)
-    dbs = os.path.join(GOLDEN, "multi", "dbs")
+    seqs = [gm.random_dna(rng, 300) for _ in range(16)]
+    dbs = build_directory(ctx, oracle, tmp_path, seqs)
     fresh = [gm.random_dna(rng, 400) for _ in range(5)]
-    reads = [s for _, s in oracle.read_sequences(os.path.join(GOLDEN, "multi", "reads.fastq"))]
-    reads = [reads[int(i)] for i in rng.choice(len(reads), size=3, replace=False)]
-    queries = reads + [fresh[0][30:200], fresh[1][100:300], fresh[0][:60] + fresh[1][:60], fresh[2][5:150], fresh[3][250:330], "ACGT"]
-    plan = ["add", "add", "add", "add", "retire_file", "retire_live", "compact", "compact", "save_reopen", "export"]
-    rng.shuffle(plan)
+    picks = [int(i) for i in rng.choice(16, size=3, replace=False)]
+    queries = [seqs[picks[0]][10:150], seqs[picks[1]][50:250], seqs[picks[2]], fresh[0][30:200], fresh[1][100:300], fresh[0][:60] + fresh[1][:60],
+               fresh[2][5:150], fresh[3][250:330], seqs[2][:60] + seqs[7][:60], "ACGT"]
+    plan = database_plan(rng, seed)
+    assert plan.index("retire_file") < plan.index("fold") < plan.index("merge") < min(len(plan) - 1 - plan[::-1].index(w) for w in ("retire_file", "compact", "save_reopen"))
+    assert (plan.index("fold") < plan.index("reserve") < plan.index("merge")) == (seed == 1)
+    params_of = lambda g: (g.params.kmer_len, g.params.num_hash, g.params.log_2_filter_len, g.params.hash_func)
     db = ka.FileDatabase(ctx, [dbs], headroom=64)
     try:
         model = DatabaseModel(oracle, db.files)
+        assert [key[2] for key in model.keys()] == [10, 12, 11] and [len(s) for _, s in model.groups] == [7, 5, 4]
         check_database(db, model, queries)
-        n_added = 0
+        n_added, dup = 0, None
         for step, what in enumerate(plan):
             keys = model.keys()
-            assert [(g.params.kmer_len, g.params.num_hash, g.params.log_2_filter_len, g.params.hash_func) for g in db.groups] == keys
-            live = [a for key in keys for a, _ in model.live.get(key, [])]
+            assert [params_of(g) for g in db.groups] == keys
+            live = model.live()
             if what == "add":
                 gi = int(rng.integers(len(keys)))
                 acc = "SRR99%d%02d" % (seed, n_added)
                 assert db.add_sample(acc, [fresh[n_added % len(fresh)]], group=gi)[0] == gi
-                model.add(keys[gi], acc, fresh[n_added % len(fresh)])
+                model.add(gi, acc, fresh[n_added % len(fresh)])          # (behind a fold: hashed at the group's new length)
                 n_added += 1
-            elif what == "retire_live" and live:
-                acc = live[int(rng.integers(len(live)))]
-                db.retire_sample(acc)
-                model.retire(acc)
+            elif what == "add_dup":
+                # a live sample under a FILE sample's accession: the file's comes first in report order
+                dup = [s for s in model.report() if s[4][0] == 0][int(rng.integers(3))][1]
+                gi = int(rng.integers(len(keys)))
+                assert db.add_sample(dup, [fresh[4]], group=gi)[0] == gi
+                model.add(gi, dup, fresh[4])
+            elif what in ("retire_dup", "retire_dup2"):
+                carriers = [s for s in model.report() if s[1] == dup]
+                assert len(carriers) == (2 if what == "retire_dup" else 1)
+                gi, origin = model.retire(dup)
+                assert origin == carriers[0][4] and db.retire_sample(dup)[0] == gi
+                if what == "retire_dup":
+                    assert origin[0] == 0 and [s[4][0] for s in model.report() if s[1] == dup] == [1]      # the file's went, the live one stays
+                else:
+                    with pytest.raises(KeyError):
+                        db.retire_sample(dup)
+            elif what == "retire_live" and [a for a in live if a != dup]:
+                acc = [a for a in live if a != dup][int(rng.integers(len([a for a in live if a != dup])))]
+                assert db.retire_sample(acc)[0] == model.retire(acc)[0]
                 with pytest.raises(KeyError):
                     db.retire_sample(acc)
-            elif what in ("retire_file", "retire_live"):
-                acc = model.files_samples[int(rng.integers(len(model.files_samples)))][1]
-                db.retire_sample(acc)
-                model.retire(acc)
+            elif what in ("retire_file", "retire_live", "retire_last_group"):
+                mine = [s for s in model.report() if s[4][0] == 0 and s[1] != dup and (what != "retire_last_group" or s[3] == len(keys) - 1)]
+                acc = mine[int(rng.integers(len(mine)))][1]
+                assert db.retire_sample(acc)[0] == model.retire(acc)[0]
             elif what == "compact":
                 stats = db.compact()
-                assert [s["columns"] for s in stats] == [len(model.group(key)) for key in keys]
-                assert [g.column_span for g in db.groups] == [(len(model.group(key)) + 7) // 8 * 8 for key in keys]
+                assert [s["columns"] for s in stats] == [len(samples) for _, samples in model.groups]
+                assert [g.column_span for g in db.groups] == [(len(samples) + 7) // 8 * 8 for _, samples in model.groups]
+            elif what == "fold":
+                old = list(db.groups)
+                done = model.fold(10)
+                stats = db.fold(10)
+                assert [(s["log_2_before"], s["log_2_after"]) for s in stats] == [(keys[gi][2], 10) for gi in done] and len(done) == 2
+                assert all((db.groups[gi] is not old[gi]) == (gi in done) and bool(old[gi]._h) == (gi not in done) for gi in range(len(old)))
+                assert len(model.keys()) == len(keys) and len(set(model.keys())) == len(keys) - 1      # two groups share their parameters until a merge
+                assert db.fold(10) == []
+            elif what == "merge":
+                old, strides = list(db.groups), [g.row_stride for g in db.groups]
+                made = model.merge()
+                assert db.merge_groups() == len(old) - len(made) == 1
+                assert [params_of(g) for g in db.groups] == model.keys()
+                for g, members in zip(db.groups, made):
+                    if len(members) > 1:
+                        assert 8 * g.row_stride == sum(8 * strides[gi] for gi in members) and not any(old[gi]._h for gi in members)
+                    else:
+                        assert g is old[members[0]]
+                assert db.merge_groups() == 0
+            elif what == "reserve":
+                old = list(db.groups)
+                h = max(g.room for g in old) + 1
+                stats = db.reserve(h)
+                assert all(g.room >= h for g in db.groups) and not any(g in old for g in db.groups) and not any(g._h for g in old)
+                assert len(stats) == len(old) and [s["columns"] for s in stats if s] == [len(samples) for _, samples in model.groups if samples]
+                assert db.reserve(h) == []
             elif what == "save_reopen":
                 out = str(tmp_path / ("saved%d" % step))
                 assert db.save(out)
@@ -353,14 +479,21 @@ def test_file_database_sequences(ka, ctx, oracle, tmp_path, seed):
             else:
                 assert what == "export"
                 report = model.report()
-                picks = [report[int(i)] for i in rng.choice(len(report), size=3, replace=False)] + [(key, a, c) for key in keys for a, c in model.live.get(key, [])[:1]]
-                written = db.export_samples([a for _, a, _ in picks], str(tmp_path / ("bloom%d" % step)))
+                picks = [report[int(i)] for i in rng.choice(len(report), size=3, replace=False)] + [s for s in report if s[4][0] == 1][:2]
+                first = {}
+                for s in report:
+                    first.setdefault(s[1], s)
+                picks = list({s[1]: first[s[1]] for s in picks}.values())      # (an accession carried twice: the first in report order is written, once)
+                written = db.export_samples([s[1] for s in picks], str(tmp_path / ("bloom%d" % step)))
                 assert len(written) == len(picks)
-                for key, a, col in picks:
+                for key, a, col, _, _ in picks:
                     params, _, info, bits = oracle.read_bloom(os.path.join(str(tmp_path / ("bloom%d" % step)), a + ".bloom"))
                     assert params == (key[0], key[2], key[1], key[3]) and info.csv_string() == a
                     assert np.array_equal(gm.columns_of(np.ascontiguousarray(bits)[None, :], key[2])[:, 0], col), (seed, step, a)
-            check_database(db, model, queries)
+            try:
+                check_database(db, model, queries)
+            except AssertionError as e:
+                raise AssertionError("after step %d (%s) of seed %d: %s" % (step, what, seed, plan)) from e
         # at the end: the other forms, and the saved directory answers the same
         report = model.report()
         counts, nks = model.counts(queries)
@@ -379,10 +512,10 @@ def test_file_database_sequences(ka, ctx, oracle, tmp_path, seed):
         near = db.similar_samples(asked, 3)
         for (a, recs), want_a in zip(near, asked):
             key = [s[0] for s in report if s[1] == a][0]
-            mine = model.group(key)
-            A = [s[2] for s in mine if s[1] == a][0]
+            mine = [s for gi in range(len(model.groups)) if model.keys()[gi] == key for s in model.group(gi)]      # (group order, then column order)
+            A = [s[2] for s in report if s[1] == a][0]
             cand = []
-            for j, (_, a2, col) in enumerate(mine):
+            for j, (_, a2, col, _, _) in enumerate(mine):
                 shared, fb, cb = int((A & col).sum()), int(A.sum()), int(col.sum())
                 union = fb + cb - shared
                 cand.append((-(shared / union if union > 0 else 0.0), j, a2, shared, fb, cb))
