@@ -344,6 +344,52 @@ typedef struct {
 int kwage_group_copy_columns(kwage_group *dst, kwage_group *src, const uint64_t *columns, uint64_t n,
                              uint32_t flags, uint64_t *first_column, kwage_copy_stats *stats);
 
+/* Union of columns, no counterpart in the reference: n_sets new columns of the resident group dst, each the row-wise OR
+ * of listed columns of the resident group src, made on the device in one pass over the rows.  A row index is
+ * hash % filter_len (kwage.cpp:411-412), so the OR of the filters of k-mer sets A and B is the filter of A u B: the new
+ * column is byte for byte the filter the reference would have built from the members' reads together -- several runs
+ * of one biosample as one sample, one pan-filter of a species' samples -- without kwage_group_export_filters, an OR on the
+ * host and kwage_group_insert_filters.
+ *   - new column *first_column + j of dst is, in every row, the OR of src's columns
+ *     columns[set_offsets[j] .. set_offsets[j + 1]); set_offsets has n_sets + 1 entries and starts at 0.  A member may stand
+ *     in several sets; a member repeated within a set is folded; a set of one member is a copy of that column;
+ *   - dst != src: placement, the bits written and the state afterwards are kwage_group_copy_columns', hence the live
+ *     insert's: behind an open tail at bit granularity, else at the next 16-byte boundary of the row; bits below
+ *     *first_column are kept from memory, bits at and above the new tail are written as zero to the end of the last
+ *     32-bit word touched; the valid mask, span, open tail and column count follow, and a finalized dst re-samples its
+ *     bit densities.  dst is afterwards bit for bit what kwage_group_insert_filters(dst, <the ORs of the members' exported
+ *     filters>) would have made of it;
+ *   - dst == src is allowed -- a union usually lands in the group that holds its members.  The new columns then start at
+ *     the next 16-byte boundary of the row ALSO behind an open tail: the up to 127 columns skipped become pad columns, as
+ *     between two file blocks (kwage_group_compact closes them), and the tail is open at *first_column + n_sets
+ *     afterwards.  Members lie in valid columns below the old span and every 16-byte unit written lies wholly above it,
+ *     so the kernel never reads a byte it writes: no ordering, fence or atomic is needed.  The cost is the pad: a call
+ *     per union wastes up to 127 columns each time -- batch many unions into one call;
+ *   - src's own columns are never changed.  Bits that kwage_group_set_bits left in pad or retired columns never travel:
+ *     the masks name member bits only;
+ *   - the host folds the lists into distinct (source dword of the row, 32-bit mask) pairs per set: members that share a
+ *     dword cost one load.  One lane makes one 16-byte unit of one destination row and stores it once; dst is read only by
+ *     the owners of a row's first and last unit, for what they keep.  No atomics;
+ *   - before and after kwage_group_finalize, on either group;
+ *   - flags: KWAGE_SEARCH_TIMING fills stats->kernel_ms with the HIP-event duration of the kernel; other bits are
+ *     ignored.  stats may be NULL.
+ * Errors, all found before a byte is written or allocated -- *first_column and *stats are not written, both groups are as
+ * before -- in this order: KWAGE_ERR_ARG for a NULL dst, src, columns, set_offsets or first_column; n_sets == 0;
+ * set_offsets[0] != 0, a decreasing offset or an empty set; groups of different contexts; a sparse group on either side;
+ * kmer_len, num_hash, log_2_filter_len or hash_func differing; then KWAGE_ERR_STATE while a search is pending on the
+ * context; then KWAGE_ERR_ARG again for a member at or beyond src's span, a pad or retired column (the first offender in
+ * list order); more than 2^32 - 1 members (or entries); more sets than dst's capacity holds
+ * (*first_column + n_sets > 8 * row_stride).  Synchronous; runs on the context's first stream. */
+typedef struct {
+	uint64_t first_column, sets, members;  /* members: list entries as given                         */
+	uint64_t entries;                      /* (source dword, mask) pairs after folding               */
+	uint64_t first_unit, units;            /* 16-byte units of a destination row written             */
+	uint64_t bytes_written;
+	float kernel_ms;                       /* with KWAGE_SEARCH_TIMING, else 0                       */
+} kwage_union_stats;
+int kwage_group_union_columns(kwage_group *dst, kwage_group *src, const uint64_t *columns, const uint64_t *set_offsets, uint32_t n_sets,
+                              uint32_t flags, uint64_t *first_column, kwage_union_stats *stats);
+
 /* ------------------------------------------------------------------------------------
  * Query batch: raw sequences (any case, any characters -- exactly what the reference hands to
  * search(), kwage.cpp:119,137), concatenated, uploaded once and kept resident in HBM.

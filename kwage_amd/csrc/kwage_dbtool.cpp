@@ -25,6 +25,15 @@
 //                                                                   length.  stderr: the share of set bits per column before
 //                                                                   and after and the false-positive rate it buys; exit code 1,
 //                                                                   nothing written, for a length not below the file's
+//   kwage_dbtool union <out.db> <in.db> <NEW>=<ACC1>,<ACC2>[,...]...  in.db loaded into a group, per argument one new column, the OR
+//                                                                   of the named samples' columns made on the device
+//                                                                   (kwage_group_union_columns): the Bloom filter of their reads
+//                                                                   together.  Everything saved as one file; members keep their
+//                                                                   records, a new column gets its run accession <NEW> and no
+//                                                                   other field.  stderr: per new column the bits set and the
+//                                                                   false-positive rate fill^num_hash; exit code 1, nothing
+//                                                                   written, when a member is not in the file
+//   kwage_dbtool merge <out.db> <in.db> <NEW>=<ACC1>,<ACC2>[,...]...  the same, with the members dropped from the output
 //   kwage_dbtool mkbloom <out.bloom> <accession> <k> <log2 len|0> <num hash|0> <seq file> [p]
 //                                                                   exact k-mer set of a FASTA/FASTQ -> .bloom; 0 0 = pick the
 //                                                                   parameters with optimal_bloom_param(p, default 0.25)
@@ -62,6 +71,7 @@ static int usage()
 		"       kwage_dbtool drop <out.db> <in.db> <run accession>...\n"
 		"       kwage_dbtool extract <out dir> <in.db> [<run accession>...]\n"
 		"       kwage_dbtool fold <out.db> <in.db|.dbz> <log2 len>\n"
+		"       kwage_dbtool union|merge <out.db> <in.db> <new accession>=<run accession>[,<run accession>...]...\n"
 		"       kwage_dbtool mkbloom <out.bloom> <accession> <k> <log2 len|0> <num hash|0> <seq file> [p]\n"
 		"       kwage_dbtool countbloom <out.bloom> <accession> <k> <min count> <seq file>... [-p p] [-l min log2] [-L max log2]\n");
 	return 2;
@@ -225,6 +235,77 @@ static int fold_db(kwage_ctx *ctx, const char *out_db, const char *in_db, uint32
 	return rc;
 }
 
+// `union` and `merge`: in.db plus one column per NEW=ACC1,ACC2[,...] -- the OR of the members' columns, made on the device in
+// the group that holds them (kwage_group_union_columns) -- with the members kept (`union`) or dropped (`merge`).
+static int union_db(kwage_ctx *ctx, const char *what, const char *out_db, const char *in_db, char **specs, int n, bool drop_members)
+{
+	// NEW=ACC1,ACC2,...: the new run accession and its members
+	std::vector<std::string> names;
+	std::vector<std::vector<std::string>> members(n);
+	for(int i = 0; i < n; ++i){
+		const std::string spec = specs[i];
+		const size_t eq = spec.find('=');
+		if(eq == std::string::npos || eq == 0 || eq + 1 >= spec.size()){ return usage(); }
+		names.push_back(spec.substr(0, eq));
+		for(size_t at = eq + 1; at <= spec.size(); ){
+			const size_t comma = std::min(spec.find(',', at), spec.size());
+			if(comma == at){ return usage(); }
+			members[i].push_back(spec.substr(at, comma - at));
+			at = comma + 1;
+		}
+	}
+	std::vector<char*> wanted;
+	for(auto &m : members){ for(std::string &a : m){ wanted.push_back(&a[0]); } }
+	std::vector<std::string> have;
+	int rc = read_accessions(what, in_db, wanted.data(), (int)wanted.size(), have);
+	if(rc){ return rc; }
+	// a member is the first column that carries the accession
+	std::vector<uint64_t> columns, offsets(1, 0);
+	std::vector<bool> is_member(have.size(), false);
+	for(const auto &m : members){
+		for(const std::string &a : m){
+			const uint64_t j = (uint64_t)(std::find(have.begin(), have.end(), a) - have.begin());
+			columns.push_back(j);
+			is_member[j] = true;
+		}
+		offsets.push_back(columns.size());
+	}
+	kwage_db_header h;
+	kwage_group *g = NULL;
+	if((rc = load_db(ctx, in_db, (uint64_t)n, &h, &g))){ return rc; }
+	uint64_t first = 0;
+	kwage_union_stats st;
+	if(kwage_group_union_columns(g, g, columns.data(), offsets.data(), (uint32_t)n, KWAGE_SEARCH_TIMING, &first, &st)){ kwage_group_destroy(g); return die(what); }
+	// members keep their records; a new column gets its run accession and no other field
+	std::vector<kwage_sample_info> infos(n, kwage_sample_info{});
+	std::vector<kwage_save_column> cols;
+	for(uint32_t j = 0; j < h.num_filter; ++j){
+		if(!(drop_members && is_member[j])){ cols.push_back(kwage_save_column{j, in_db, j, NULL}); }
+	}
+	for(int i = 0; i < n; ++i){
+		infos[i].run_accession = names[i].c_str();
+		cols.push_back(kwage_save_column{first + (uint64_t)i, NULL, 0, &infos[i]});
+	}
+	rc = save_columns(g, out_db, cols);
+	// what a union costs: the share of set bits of the new column, and the rate at which an absent k-mer passes it
+	if(!rc && kwage_group_finalize(g)){ rc = die("finalize"); }
+	std::vector<uint32_t> bits(kwage_group_column_span(g), 0u);
+	if(!rc && kwage_group_column_bits(g, bits.data())){ rc = die("column bits"); }
+	if(!rc){
+		const double rows = (double)(1ull << h.log_2_filter_len);
+		for(int i = 0; i < n; ++i){
+			uint32_t top = 0;
+			for(uint64_t c = offsets[i]; c < offsets[i + 1]; ++c){ top = std::max(top, bits[columns[c]]); }
+			const double fill = (double)bits[first + (uint64_t)i]/rows;
+			fprintf(stderr, "%s %s: %zu members, %u bits set of %.0f (largest member %u), fill %.6f, false-positive rate %.6g\n", what, names[i].c_str(),
+			        members[i].size(), bits[first + (uint64_t)i], rows, top, fill, pow(fill, (double)h.num_hash));
+		}
+		fprintf(stderr, "%s: %llu entries, %llu bytes written, union kernel %.3f ms\n", what, (unsigned long long)st.entries, (unsigned long long)st.bytes_written, st.kernel_ms);
+	}
+	kwage_group_destroy(g);
+	return rc;
+}
+
 int main(int argc, char **argv)
 {
 	if(argc < 3){ return usage(); }
@@ -257,7 +338,7 @@ int main(int argc, char **argv)
 	}
 
 	// the remaining commands run on the device
-	if(cmd != "build" && cmd != "repack" && cmd != "append" && cmd != "drop" && cmd != "extract" && cmd != "fold" && cmd != "mkbloom" && cmd != "countbloom"){ return usage(); }
+	if(cmd != "build" && cmd != "repack" && cmd != "append" && cmd != "drop" && cmd != "extract" && cmd != "fold" && cmd != "union" && cmd != "merge" && cmd != "mkbloom" && cmd != "countbloom"){ return usage(); }
 	kwage_ctx *ctx = NULL;
 	const char *dev = getenv("KWAGE_DEVICE");
 	if(kwage_init(dev ? atoi(dev) : 0, &ctx)){ return die("init"); }
@@ -284,6 +365,9 @@ int main(int argc, char **argv)
 	}
 	else if(cmd == "fold" && argc == 5){
 		rc = fold_db(ctx, argv[2], argv[3], (uint32_t)atoi(argv[4]));
+	}
+	else if((cmd == "union" || cmd == "merge") && argc >= 5){
+		rc = union_db(ctx, cmd.c_str(), argv[2], argv[3], argv + 4, argc - 4, cmd == "merge");
 	}
 	else if(cmd == "mkbloom" && argc >= 8){
 		kwage_seqfile *sf = NULL;

@@ -276,6 +276,26 @@ class Group:
         self._inserted(first.value, int(st.columns))
         return first.value, {f: getattr(st, f) for f, _ in native.CopyStats._fields_}
 
+    def union_columns(self, sets: Sequence[Sequence[int]], src: Optional["Group"] = None, timing: bool = False) -> Tuple[int, dict]:
+        """New columns of this group, each the row-wise OR of listed columns of `src` (this group where src is None), made on
+        the device (kwage_group_union_columns): column first_column + j is the Bloom filter of the union of the samples in
+        sets[j].  From another group the columns are placed as insert_filters() places its filters; within one group they
+        start at the next 16-byte boundary of the row, also behind an open tail (the columns skipped are pad columns:
+        batch many unions into one call).  `src`'s own columns are not changed.  Returns (first_column, stats)."""
+        src = self if src is None else src
+        sets = [np.ascontiguousarray(s, dtype=np.uint64).reshape(-1) for s in sets]
+        offsets = np.zeros(len(sets) + 1, dtype=np.uint64)
+        if sets:
+            offsets[1:] = np.cumsum([s.size for s in sets], dtype=np.uint64)
+        columns = np.concatenate(sets) if sets else np.zeros(0, dtype=np.uint64)
+        columns = columns if columns.size else np.zeros(1, dtype=np.uint64)      # (an empty list is refused by the call: the pointer is not NULL)
+        first = C.c_uint64()
+        st = native.UnionStats()
+        check(lib().kwage_group_union_columns(self._h, src._h, columns.ctypes.data_as(C.c_void_p), offsets.ctypes.data_as(C.c_void_p), len(sets),
+                                              SEARCH_TIMING if timing else 0, C.byref(first), C.byref(st)))
+        self._inserted(first.value, int(st.sets))
+        return first.value, {f: getattr(st, f) for f, _ in native.UnionStats._fields_}
+
     @staticmethod
     def _save_columns(columns: Sequence[int], sources: Sequence):
         """The kwage_save_column array of save_db() and export_bloom_files(): (array, what its entries point to -- to be
@@ -1027,11 +1047,65 @@ class FileDatabase(Database):
         else:
             raise KeyError("no sample with run accession %s in the database" % accession)
         self.groups[gi].retire_columns([col])
-        if isinstance(path, _LiveBlock):
+        if isinstance(path, _LiveBlock) and len(path.accessions) == 1:
             self._layout[gi] = [e for e in self._layout[gi] if e[2] is not path]
-        else:
+        else:                                         # (a file's column, or one of a live block of several: union_samples())
             self._retired.add((gi, col))
         return gi, col
+
+    def union_samples(self, unions: Sequence[Tuple[str, Sequence[str]]], retire: bool = False) -> List[Tuple[int, int]]:
+        """New samples that are unions of samples of the resident database, made on the device (Group.union_columns): for
+        every (new_accession, member_accessions) one new column, the OR of the members' columns -- the Bloom filter of all
+        their reads together, recorded under new_accession.  A member is the first sample in report order carrying the
+        accession (retire_sample()'s rule); all members of one union must lie in one group.  One device call per group, the
+        new samples of a group recorded in ONE live block, which save(), export_samples(), the searches and
+        similar_samples() see like add_sample()'s.  retire=True withdraws the members afterwards: the "merge".  A group
+        needs room for its unions behind the next 16-byte boundary of its row -- up to 127 columns more than their number
+        (FileDatabase(..., headroom=n), reserve()).  KeyError for an unknown accession, ValueError for a union across two
+        groups, both before anything changes.  Returns [(group index, column)] in the order of `unions`."""
+        first = {}
+        for gi, col, path, c in self._samples():
+            first.setdefault(self._accession(path, c), (gi, col))
+        per_group = {}                                # group index -> [(place in `unions`, new accession, member columns)]
+        for i, (new, members) in enumerate(unions):
+            members = list(members)
+            if not members:
+                raise ValueError("union %s has no members" % new)
+            for a in members:
+                if a not in first:
+                    raise KeyError("no sample with run accession %s in the database" % a)
+            gi = first[members[0]][0]
+            for a in members:
+                if first[a][0] != gi:
+                    pa, pb = self.groups[gi].params, self.groups[first[a][0]].params
+                    raise ValueError("union %s: %s lies in group %d (kmer_len %d, num_hash %d, log_2_filter_len %d) and %s in group %d "
+                                     "(kmer_len %d, num_hash %d, log_2_filter_len %d): fold() and merge_groups() first"
+                                     % (new, members[0], gi, pa.kmer_len, pa.num_hash, pa.log_2_filter_len,
+                                        a, first[a][0], pb.kmer_len, pb.num_hash, pb.log_2_filter_len))
+            per_group.setdefault(gi, []).append((i, new, [first[a][1] for a in members]))
+        for gi, todo in per_group.items():            # room, before anything changes
+            g = self.groups[gi]
+            landing = (g.row_bytes + 15) // 16 * 16 * 8
+            if landing + len(todo) > 8 * g.row_stride:
+                raise native.KwageError(-1, "union_samples: group %d has no room for %d columns behind column %d of a row of %d: reserve() first"
+                                        % (gi, len(todo), landing, 8 * g.row_stride))
+        out = [None] * len(unions)
+        for gi, todo in per_group.items():
+            col, _ = self.groups[gi].union_columns([cols for _, _, cols in todo])
+            self._layout[gi].append((col, len(todo), _LiveBlock([new for _, new, _ in todo]), 0))
+            for j, (i, _, _) in enumerate(todo):
+                out[i] = (gi, col + j)
+        if retire:
+            gone = {}
+            for gi, todo in per_group.items():
+                for _, _, cols in todo:
+                    gone.setdefault(gi, set()).update(cols)
+            for gi, cols in gone.items():
+                self.groups[gi].retire_columns(sorted(cols))
+                single = {e[0] for e in self._layout[gi] if isinstance(e[2], _LiveBlock) and len(e[2].accessions) == 1 and e[0] in cols}
+                self._layout[gi] = [e for e in self._layout[gi] if e[0] not in single or not isinstance(e[2], _LiveBlock)]
+                self._retired.update((gi, c) for c in cols if c not in single)
+        return out
 
     def compact(self) -> List[dict]:
         """Close the gaps that retired samples and the files' alignment pads leave, in every resident group

@@ -100,6 +100,11 @@ class CopyStats(C.Structure):
                 ("units", C.c_uint64), ("bytes_written", C.c_uint64), ("kernel_ms", C.c_float)]
 
 
+class UnionStats(C.Structure):
+    _fields_ = [("first_column", C.c_uint64), ("sets", C.c_uint64), ("members", C.c_uint64), ("entries", C.c_uint64),
+                ("first_unit", C.c_uint64), ("units", C.c_uint64), ("bytes_written", C.c_uint64), ("kernel_ms", C.c_float)]
+
+
 class BloomCounterStats(C.Structure):
     _fields_ = [("num_valid_kmer", C.c_uint64), ("num_bp", C.c_uint64), ("positions", C.c_uint64),
                 ("occurrences_committed", C.c_uint64), ("chunks", C.c_uint64), ("rounds", C.c_uint64),
@@ -168,6 +173,7 @@ _SIGNATURES = [
     ("kwage_group_compact", C.c_int, [_P, C.c_uint32, C.POINTER(C.c_uint64), C.c_uint64, C.POINTER(CompactStats)]),
     ("kwage_group_fold", C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(_P), C.POINTER(FoldStats)]),
     ("kwage_group_copy_columns", C.c_int, [_P, _P, _P, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(CopyStats)]),
+    ("kwage_group_union_columns", C.c_int, [_P, _P, _P, _P, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(UnionStats)]),
     ("kwage_batch_create", C.c_int, [_P, C.c_char_p, _P, C.c_uint32, C.POINTER(_P)]),
     ("kwage_batch_destroy", None, [_P]),
     ("kwage_batch_num_queries", C.c_uint32, [_P]),
