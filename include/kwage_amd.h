@@ -362,7 +362,12 @@ int kwage_group_copy_columns(kwage_group *dst, kwage_group *src, const uint64_t 
  *   - dst == src is allowed -- a union usually lands in the group that holds its members.  The new columns then start at
  *     the next 16-byte boundary of the row ALSO behind an open tail: the up to 127 columns skipped become pad columns, as
  *     between two file blocks (kwage_group_compact closes them), and the tail is open at *first_column + n_sets
- *     afterwards.  Members lie in valid columns below the old span and every 16-byte unit written lies wholly above it,
+ *     afterwards.  The skipped columns are not written: they hold what the memory held -- zero behind a fresh insert up
+ *     to the end of its last 32-bit word, but whatever a compaction that kept the memory (no valid column left) or
+ *     kwage_group_set_bits left there beyond it -- and come below the span as dead columns with those bits: no search,
+ *     kwage_group_column_bits, fold, compaction, save or export counts them.  Likewise the bits above the last 32-bit
+ *     word the union touches are kept, as behind any live insert, and show when the span grows over them.
+ *     Members lie in valid columns below the old span and every 16-byte unit written lies wholly above it,
  *     so the kernel never reads a byte it writes: no ordering, fence or atomic is needed.  The cost is the pad: a call
  *     per union wastes up to 127 columns each time -- batch many unions into one call;
  *   - src's own columns are never changed.  Bits that kwage_group_set_bits left in pad or retired columns never travel:

@@ -4,6 +4,9 @@ five alive at a time, under group_model's mutators (each with on=<name>) and the
   fold        GroupModel.fold of `src` at `L2` under a new name (kwage_group_fold, Group.fold)
   copy        copy_model.copy between two groups of equal parameters (kwage_group_copy_columns, Group.copy_columns_from);
               groups whose filter lengths differ -- a source and its own fold -- refuse it
+  union       union_model.union of member lists `sets` of `src` into `on`, which may be the same name
+              (kwage_group_union_columns, Group.union_columns); refused between filter lengths as the copy is.  sequence()
+              makes none: tests/union_walk.py walks with it
   new         a group created natively at a given filter length: the partner a fold copies to and from
   close       the group is gone; whatever was folded or copied from it lives on
   checkpoint  where the GPU test runs every search form on one finalized group
@@ -35,6 +38,7 @@ import numpy as np
 
 import copy_model as cm
 import group_model as gm
+import union_model as um
 
 ERR_ARG, ERR_STATE = gm.ERR_ARG, gm.ERR_STATE
 NARROW, WIDE = (8, 2000, 15, 2), (11, 8500, 31, 5)         # (L, capacity, k, num_hash) of the root
@@ -94,6 +98,11 @@ class Family:
             if dst is not src and dst.L != src.L:
                 return ERR_ARG
             return cm.copy(dst, src, op.cols)
+        if op.kind == "union":
+            dst, src = self.models[op.on], self.models[op.src]
+            if dst is not src and dst.L != src.L:
+                return ERR_ARG
+            return um.union(dst, src, op.sets)
         if op.kind == "checkpoint":
             return 0
         return self.models[op.on].apply(op)

@@ -89,8 +89,9 @@ def as_one(seq, L):
     return types.SimpleNamespace(shape=(L, cap, k, nh))
 
 
-def call(ka, ctx, oracle, groups, models, op, seq, tmp_path, step):
-    """The step on the device groups -> what the family returns for it (the error code where the call is refused)."""
+def call(ka, ctx, oracle, groups, models, op, seq, tmp_path, step, stats=None):
+    """The step on the device groups -> what the family returns for it (the error code where the call is refused); a
+    union's stats go into `stats`."""
     from kwage_amd.native import lib
     _, cap, k, nh = seq.shape
     try:
@@ -107,6 +108,11 @@ def call(ka, ctx, oracle, groups, models, op, seq, tmp_path, step):
         g = groups[op.on]
         if op.kind == "copy":
             return g.copy_columns_from(groups[op.src], op.cols)[0]
+        if op.kind == "union":
+            first, st = g.union_columns(op.sets, groups[op.src])
+            if stats is not None:
+                stats.update(st)
+            return first
         if op.kind == "add_columns":
             return g.add_columns(op.image, op.nf)
         if op.kind == "insert":
@@ -148,10 +154,56 @@ def checkpoint(ka, ctx, oracle, g, m, op, seq):
     assert not any(ctx.scratch_nonzero().values())
 
 
+def check_every_group(groups, fam, op, packed, what):
+    """The state of EVERY group alive behind a step, all of it, exact; packed: name -> the model's rows packed, until a step
+    names the group."""
+    assert sorted(groups) == sorted(fam.models), what          # (a refused fold made no group)
+    for name in (op.on, getattr(op, "src", None)):
+        packed.pop(name, None)
+    for name, m in fam.models.items():
+        g = groups[name]
+        assert (g.column_span, g.num_columns, g.row_bytes, g.row_stride) == (m.span, m.num_columns, m.span // 8, m.stride), (what, name)
+        assert g.params.log_2_filter_len == m.L and np.array_equal(g.real_columns(), m.real), (what, name)
+        assert g.room == max(0, m.room()), (what, name, g.room, m.room())
+        if m.span:
+            if name not in packed:
+                packed[name] = m.packed()
+            rows = g.read_rows(np.arange(m.nrows))
+            assert np.array_equal(rows, packed[name]), (what, name, np.argwhere(rows != packed[name])[:5])
+    if hasattr(op, "twin"):               # fold_twice, union_fold_commutes: the two device groups are the same
+        a, b = groups[op.on], groups[op.twin]
+        nrows = np.arange(fam.models[op.on].nrows)
+        assert (a.column_span, a.num_columns) == (b.column_span, b.num_columns) and np.array_equal(a.real_columns(), b.real_columns())
+        assert np.array_equal(a.read_rows(nrows), b.read_rows(nrows)), what
+
+
+def round_trips(ka, ctx, groups, fam, seq, tmp_path, others):
+    """The end: every group's real columns through a file and back, and through export and insert."""
+    _, cap, k, nh = seq.shape
+    seed = seq.seed
+    for name, m in fam.models.items():
+        g, real = groups[name], np.flatnonzero(m.real)
+        if not real.size:
+            continue
+        nrows = np.arange(m.nrows)
+        dense = cc.reference(m.bits, m.real)
+        path = str(tmp_path / ("saved_%s.db" % name))
+        g.save_db(path, real.tolist(), [{"run_accession": "SRR%d" % (j + 1)} for j in range(real.size)])
+        loaded = ka.Group(ctx, k, nh, m.L, cap)
+        others.append(loaded)
+        assert loaded.add_db_file(path) == (0, real.size)
+        assert np.array_equal(loaded.read_rows(nrows), dense), (seed, name)
+        filters = g.export_filters(real)
+        assert np.array_equal(filters, gm.filters_of(m.bits[:, real])), (seed, name)
+        third = ka.Group(ctx, k, nh, m.L, cap)
+        others.append(third)
+        assert third.insert_filters(filters) == 0
+        assert np.array_equal(third.read_rows(nrows), dense), (seed, name)
+
+
 @pytest.mark.parametrize("seed", SEEDS)
 def test_sequence(ka, ctx, oracle, tmp_path, seed):
     seq = fm.sequence(seed)
-    _, cap, k, nh = seq.shape
     fam, groups, others = fm.Family(seq.shape), {}, []
     packed = {}                                   # name -> the model's rows packed, until a step names the group
     try:
@@ -170,43 +222,8 @@ def test_sequence(ka, ctx, oracle, tmp_path, seed):
                 assert np.array_equal(got[0], want[0]) and got[1] == {key: want[1][key] for key in STAT_KEYS}, what
             else:
                 assert got == want and op.refused() == (isinstance(got, int) and got < 0), (what, got, want)
-            assert sorted(groups) == sorted(fam.models), what          # (a refused fold made no group)
-            for name in (op.on, getattr(op, "src", None)):
-                packed.pop(name, None)
-            # the state of EVERY group alive, all of it, exact
-            for name, m in fam.models.items():
-                g = groups[name]
-                assert (g.column_span, g.num_columns, g.row_bytes, g.row_stride) == (m.span, m.num_columns, m.span // 8, m.stride), (what, name)
-                assert g.params.log_2_filter_len == m.L and np.array_equal(g.real_columns(), m.real), (what, name)
-                assert g.room == max(0, m.room()), (what, name, g.room, m.room())
-                if m.span:
-                    if name not in packed:
-                        packed[name] = m.packed()
-                    rows = g.read_rows(np.arange(m.nrows))
-                    assert np.array_equal(rows, packed[name]), (what, name, np.argwhere(rows != packed[name])[:5])
-            if hasattr(op, "twin"):               # fold_twice: the two device groups are the same
-                a, b = groups[op.on], groups[op.twin]
-                assert (a.column_span, a.num_columns) == (b.column_span, b.num_columns) and np.array_equal(a.real_columns(), b.real_columns())
-                assert np.array_equal(a.read_rows(np.arange(1 << op.L2)), b.read_rows(np.arange(1 << op.L2))), what
-        # the end: every group's real columns through a file and back, and through export and insert
-        for name, m in fam.models.items():
-            g, real = groups[name], np.flatnonzero(m.real)
-            if not real.size:
-                continue
-            nrows = np.arange(m.nrows)
-            dense = cc.reference(m.bits, m.real)
-            path = str(tmp_path / ("saved_%s.db" % name))
-            g.save_db(path, real.tolist(), [{"run_accession": "SRR%d" % (j + 1)} for j in range(real.size)])
-            loaded = ka.Group(ctx, k, nh, m.L, cap)
-            others.append(loaded)
-            assert loaded.add_db_file(path) == (0, real.size)
-            assert np.array_equal(loaded.read_rows(nrows), dense), (seed, name)
-            filters = g.export_filters(real)
-            assert np.array_equal(filters, gm.filters_of(m.bits[:, real])), (seed, name)
-            third = ka.Group(ctx, k, nh, m.L, cap)
-            others.append(third)
-            assert third.insert_filters(filters) == 0
-            assert np.array_equal(third.read_rows(nrows), dense), (seed, name)
+            check_every_group(groups, fam, op, packed, what)
+        round_trips(ka, ctx, groups, fam, seq, tmp_path, others)
     finally:
         for g in list(groups.values()) + others:
             g.close()

@@ -32,6 +32,17 @@ DatabaseModel is a list of groups in db.groups order, every sample knowing where
 from the doc-strings of _blocks and merge_groups.  On an MI355X all four seeds answer as the model says; merge_groups not
 re-indexing _retired (a local mutation) fails all four in the check behind the merge.
 
+It holds FileDatabase.union_samples as well (database_plan: union, union_dup, union_last_group, union_across -- refused
+between the fold and the merge, taken behind it --, union_of_union, retire_union_member, retire_udup): DatabaseModel.unions
+resolves every member by "first in report order" before anything changes and places the new samples, live ones, behind
+the group's others.  (Which file's samples come first in report order follows the directory listing, so the members a
+seed picks differ from one file system to the next; the steps choose among what is there.)  On an MI355X all four seeds
+answer as the model says after every step.  Two mutations, made locally: union_samples(retire=True) not updating _retired
+fails all four seeds in the union_last_group step (retire_sample of a member that is gone finds it again and
+kwage_group_retire_columns refuses "column 1 is a pad column", or _retired has no entry of the last group);
+_renumbered recording f0 for f0 + c fails all four in check_database behind the first step that cuts a block -- a
+compact or the merge -- where the search reports a sample under its block's first accession.
+
 Wall time on one MI355X, the whole -m gpu suite with each file in its own process: 953 s with this file, 934 s for the
 files the parent commit has (the same run; a process start, torch's import included, is about 11 s of every file's time);
 this file 19 s in its own process (17 s inside pytest, 11 s of them the first test's imports): no sequence takes more
@@ -261,6 +272,34 @@ class DatabaseModel:
         self.groups[gi][1].append(((1, self.n_live), accession, gm.columns_of(bits[None, :], L)[:, 0]))
         self.n_live += 1
 
+    def first(self, accession):
+        """The first sample in report order carrying the accession; KeyError where none does."""
+        for s in self.report():
+            if s[1] == accession:
+                return s
+        raise KeyError(accession)
+
+    def unions(self, unions, retire=False):
+        """FileDatabase.union_samples: [(new accession, member accessions)] -> [group index] of the new samples.  Every
+        member is resolved by "first in report order" BEFORE anything changes (KeyError for an unknown one, ValueError for
+        members in two groups); each new sample is a live one, its column the OR of its members', placed behind the
+        group's others in the order of the list; with retire the resolved members go afterwards."""
+        resolved = [[self.first(a) for a in members] for _, members in unions]
+        for members in resolved:
+            if len({s[3] for s in members}) != 1:
+                raise ValueError("members in two groups")
+        for (new, _), members in zip(unions, resolved):
+            gi = members[0][3]
+            self.groups[gi][1].append(((1, self.n_live), new, np.any([s[2] for s in members], axis=0)))
+            self.n_live += 1
+        if retire:
+            for gi, origin in {(s[3], s[4]) for members in resolved for s in members}:
+                self.groups[gi][1][:] = [s for s in self.groups[gi][1] if s[0] != origin]
+        return [members[0][3] for members in resolved]
+
+    def union(self, new_accession, member_accessions, retire=False):
+        return self.unions([(new_accession, list(member_accessions))], retire)[0]
+
     def retire(self, accession):
         """The first sample in report order carrying the accession is withdrawn -> (group index, where it came from)."""
         for key, a, c, gi, origin in self.report():
@@ -375,12 +414,26 @@ def database_plan(rng, seed):
     """The steps of a seed: the old kinds and fold, merge, reserve, add_dup shuffled together, under the order every seed
     keeps -- a retire_file before the fold, the fold before the merge (a retire in the LAST group between them, nothing
     compacted: the merge has a retired file column to re-index), and a retire, a compact and a save_reopen behind the merge.
-    Seed 1 reserves between the fold and the merge, the others behind the merge."""
-    first = ["add", "add", "retire_file", "compact", "add_dup", "export"]
-    between = ["add", "retire_dup", "retire_last_group"] + (["reserve"] if seed == 1 else [])
-    after = ["retire_live", "retire_file", "compact", "save_reopen", "add", "retire_dup2", "export"] + ([] if seed == 1 else ["reserve"])
+    Seed 1 reserves between the fold and the merge, the others behind the merge.  FileDatabase.union_samples goes with
+    them: before the fold `union` (two unions in one call: a live block of two samples; two file samples and a live one
+    are members) and `union_dup` (the new sample takes a FILE sample's accession); between the fold and the merge
+    `union_last_group` (retire=True in the last group: _retired entries and a live block of two for the merge to re-index)
+    and `union_across` (members in the two groups that share parameters since the fold: ValueError); behind the merge the
+    same `union_across` list (it succeeds), `union_of_union` (a member that is an earlier union sample),
+    `retire_union_member` (the middle sample of a live block of three, before the part's compact, which cuts the block)
+    and `retire_udup` (the accession of union_dup resolves to the file's sample)."""
+    first = ["add", "add", "retire_file", "compact", "add_dup", "export", "union", "union_dup"]
+    between = ["add", "retire_dup", "retire_last_group", "union_last_group", "union_across"] + (["reserve"] if seed == 1 else [])
+    after = ["retire_live", "retire_file", "compact", "save_reopen", "add", "retire_dup2", "export", "union_across", "union_of_union", "retire_union_member",
+             "retire_udup"] + ([] if seed == 1 else ["reserve"])
     for part in (first, between, after):
         rng.shuffle(part)
+    a, b = after.index("retire_union_member"), after.index("compact")      # (the compaction cuts the block the retire left a hole in)
+    if a > b:
+        after[a], after[b] = after[b], after[a]
+    a, b = between.index("retire_last_group"), between.index("union_last_group")      # (the union's retire leaves the last group's files to the retire before it)
+    if a > b:
+        between[a], between[b] = between[b], between[a]
     return first + ["fold"] + between + ["merge"] + after
 
 
@@ -402,11 +455,36 @@ def test_file_database_sequences(ka, ctx, oracle, tmp_path, seed):
         model = DatabaseModel(oracle, db.files)
         assert [key[2] for key in model.keys()] == [10, 12, 11] and [len(s) for _, s in model.groups] == [7, 5, 4]
         check_database(db, model, queries)
-        n_added, dup = 0, None
+        n_added, dup, udup, n_unions = 0, None, None, 0
+        across, unioned = None, []                  # the members of union_across; the accessions the union steps made, oldest first
+        protected = set()                        # accessions a later step names: the random retires leave them alone
+
+        def fresh_union():
+            nonlocal n_unions
+            n_unions += 1
+            return "SRR77%d%02d" % (seed, n_unions)
+
+        def union_call(unions, retire=False):
+            """One union_samples call against the model: the new samples' groups, their columns consecutive per group."""
+            want = model.unions(unions, retire)
+            got = db.union_samples(unions, retire=retire)
+            assert [gi for gi, _ in got] == want, (got, want)
+            for gi in set(want):
+                cols = [c for g2, c in got if g2 == gi]
+                assert cols == list(range(cols[0], cols[0] + len(cols))) and cols[0] % 128 == 0
+            unioned.extend(new for new, _ in unions)
+
+        def others_of(gi, n=None, file_only=False):
+            """The accessions of group gi's samples that resolve to themselves (dup and udup left out), file samples first:
+            n of them, or all.  (Which file's samples come first in report order is the directory listing's choice.)"""
+            mine = [s for s in model.report() if s[3] == gi and model.first(s[1])[4] == s[4] and (s[4][0] == 0 or not file_only) and s[1] not in (dup, udup)]
+            assert n is None or len(mine) >= n, (gi, n, len(mine))
+            return [s[1] for s in mine[:n]]
+
         for step, what in enumerate(plan):
             keys = model.keys()
             assert [params_of(g) for g in db.groups] == keys
-            live = model.live()
+            live = [a for a in model.live() if a not in protected]
             if what == "add":
                 gi = int(rng.integers(len(keys)))
                 acc = "SRR99%d%02d" % (seed, n_added)
@@ -435,9 +513,85 @@ def test_file_database_sequences(ka, ctx, oracle, tmp_path, seed):
                 with pytest.raises(KeyError):
                     db.retire_sample(acc)
             elif what in ("retire_file", "retire_live", "retire_last_group"):
-                mine = [s for s in model.report() if s[4][0] == 0 and s[1] != dup and (what != "retire_last_group" or s[3] == len(keys) - 1)]
+                mine = [s for s in model.report() if s[4][0] == 0 and s[1] != dup and s[1] not in protected and (what != "retire_last_group" or s[3] == len(keys) - 1)]
                 acc = mine[int(rng.integers(len(mine)))][1]
                 assert db.retire_sample(acc)[0] == model.retire(acc)[0]
+            elif what == "union":
+                # two file samples and one live sample of one group, two unions in ONE call: a live block of two samples
+                with_live = sorted({s[3] for s in model.report() if s[4][0] == 1 and model.first(s[1])[4] == s[4]})
+                if not with_live:
+                    gi = int(rng.integers(len(keys)))
+                    acc = "SRR99%d%02d" % (seed, n_added)
+                    assert db.add_sample(acc, [fresh[n_added % len(fresh)]], group=gi)[0] == gi
+                    model.add(gi, acc, fresh[n_added % len(fresh)])
+                    n_added += 1
+                    with_live = [gi]
+                gi = with_live[int(rng.integers(len(with_live)))]
+                f1, f2 = others_of(gi, 2, file_only=True)
+                lv = [s[1] for s in model.report() if s[3] == gi and s[4][0] == 1 and model.first(s[1])[4] == s[4]][0]
+                state = [(g.column_span, g.num_columns) for g in db.groups]
+                with pytest.raises(KeyError):
+                    db.union_samples([(fresh_union(), [f1, "SRR7777777"])])
+                with pytest.raises(KeyError):
+                    model.union("SRR0", [f1, "SRR7777777"])
+                assert [(g.column_span, g.num_columns) for g in db.groups] == state
+                union_call([(fresh_union(), [f1, lv, f2]), (fresh_union(), [f2, f2])])
+                protected.add(unioned[-2])                          # (union_of_union names it)
+            elif what == "union_dup":
+                # the new sample takes a FILE sample's accession: retire_sample and a later union resolve to the file's
+                files = [s for s in model.report() if s[4][0] == 0 and s[1] != dup and s[1] not in protected and s[3] != len(keys) - 1]
+                carrier = files[int(rng.integers(len(files)))]
+                udup = carrier[1]
+                protected.add(udup)
+                union_call([(udup, others_of(carrier[3], 2))])
+                unioned.pop()
+                assert [s[4][0] for s in model.report() if s[1] == udup] == [0, 1] and model.first(udup)[4] == carrier[4]
+            elif what == "retire_udup":
+                carriers = [s for s in model.report() if s[1] == udup]
+                gi, origin = model.retire(udup)
+                assert origin == carriers[0][4] and db.retire_sample(udup)[0] == gi
+                assert len([s for s in model.report() if s[1] == udup]) == len(carriers) - 1
+            elif what == "union_last_group":
+                gi = len(keys) - 1
+                f1 = others_of(gi, 1, file_only=True)[0]                     # (four file samples, at most three retired by now)
+                f2 = ([a for a in others_of(gi) if a != f1] + [f1])[0]
+                union_call([(fresh_union(), [f1, f2]), (fresh_union(), [f1])], retire=True)
+                assert any(g2 == gi for g2, _ in db._retired) and any(len(e[2].accessions) == 2 for e in db._layout[gi] if hasattr(e[2], "accessions"))
+                with pytest.raises(KeyError):
+                    db.retire_sample(f1)
+            elif what == "union_across":
+                if across is None:
+                    # members in the two groups that share their parameters since the fold: refused until they are merged
+                    assert keys[0] == keys[1]
+                    across = [others_of(0, 1, file_only=True)[0], others_of(1, 1, file_only=True)[0]]
+                    protected.update(across)
+                    state = [(g.column_span, g.num_columns) for g in db.groups]
+                    with pytest.raises(ValueError, match=r"fold\(\) and merge_groups\(\) first"):
+                        db.union_samples([(fresh_union(), [across[0]]), (fresh_union(), across)])
+                    with pytest.raises(ValueError):
+                        model.union("SRR0", across)
+                    assert [(g.column_span, g.num_columns) for g in db.groups] == state
+                else:
+                    union_call([(fresh_union(), across)])
+                    protected.difference_update(across)
+            elif what == "union_of_union":
+                # one member is an earlier union sample (a file sample by now where a save_reopen came in between)
+                earlier = unioned[0]
+                gi = model.first(earlier)[3]
+                union_call([(fresh_union(), [earlier] + [a for a in others_of(gi) if a != earlier][:1])])
+                protected.discard(earlier)
+            elif what == "retire_union_member":
+                # the middle sample of a live block of three goes; the part's compact, which follows, cuts the block in two
+                roomy = [g2 for g2 in range(len(keys)) if len(others_of(g2)) >= 2]
+                gi = roomy[int(rng.integers(len(roomy)))]
+                a, b = others_of(gi, 2)
+                block = [fresh_union() for _ in range(3)]
+                union_call([(block[0], [a]), (block[1], [a, b]), (block[2], [b])])
+                assert any(getattr(e[2], "accessions", None) == block for e in db._layout[gi])
+                assert db.retire_sample(block[1])[0] == model.retire(block[1])[0] == gi
+                assert (gi, [e for e in db._layout[gi] if getattr(e[2], "accessions", None) == block][0][0] + 1) in db._retired
+                assert "compact" in plan[step + 1:]
+                unioned.remove(block[1])
             elif what == "compact":
                 stats = db.compact()
                 assert [s["columns"] for s in stats] == [len(samples) for _, samples in model.groups]
@@ -480,6 +634,8 @@ def test_file_database_sequences(ka, ctx, oracle, tmp_path, seed):
                 assert what == "export"
                 report = model.report()
                 picks = [report[int(i)] for i in rng.choice(len(report), size=3, replace=False)] + [s for s in report if s[4][0] == 1][:2]
+                picks += [s for s in report if s[1] in unioned][-1:]                # (a union sample)
+                assert "merge" not in plan[:step] or any(s[1] in unioned for s in picks)
                 first = {}
                 for s in report:
                     first.setdefault(s[1], s)
