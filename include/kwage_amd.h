@@ -395,6 +395,56 @@ typedef struct {
 int kwage_group_union_columns(kwage_group *dst, kwage_group *src, const uint64_t *columns, const uint64_t *set_offsets, uint32_t n_sets,
                               uint32_t flags, uint64_t *first_column, kwage_union_stats *stats);
 
+/* Overlap matrix, no counterpart in the reference: for every pair of listed columns of two resident groups the number of
+ * rows in which both are set -- with M the rows x columns bit matrix, shared(i, j) = popcount(col_i AND col_j) =
+ * (M_a^T M_b)[i][j], formed as that integer matrix product on the matrix cores (v_mfma_i32_32x32x32_i8).  It is what a
+ * Jaccard index of two samples is made of, for all pairs at once: its cost does not depend on how full the filters are,
+ * it needs no row list (kwage_filterset_from_columns) and only a RESIDENT group, finalized or not.
+ *   - cell (i, j) is a uint32 at cells[i*row_elems + j]: the rows in which column cols_a[i] of a and column cols_b[j] of b
+ *     are both set.  row_elems >= the cells of a row; cells from there to row_elems are not touched; cells_dev is 4-byte
+ *     aligned.  Nothing has to be cleared beforehand;
+ *   - the lists are taken as kwage_group_export_filters takes them: any order, a column may be named more than once;
+ *   - cols_x == NULL with n_x == 0: every column 0 .. span - 1 of that group.  Pad and retired columns then give a row (or
+ *     column) of zeros, as the score matrix does.  Dead columns are taken out with the valid mask: bits that
+ *     kwage_group_set_bits or a file's pad left in them never count;
+ *   - b == NULL with cols_b == NULL and n_b == 0 is the SYMMETRIC form, a's list against itself: only the tiles (128 x 128
+ *     cells) on or above the diagonal are computed and the others are written as their mirror, so the result is symmetric
+ *     by construction; its diagonal is kwage_group_column_bits;
+ *   - b != NULL: b may be a itself or another resident group of the same context with the same kmer_len, num_hash,
+ *     log_2_filter_len and hash_func; the row strides may differ;
+ *   - the lists are cut into blocks of 32 columns: a block of 32 consecutive columns that starts at a multiple of 32 is
+ *     STRAIGHT (one dword of a row feeds it), any other is GATHERED column by column.  Where the tiles are fewer than the
+ *     device needs, the row range is cut into `splits` parts whose partial tiles (a block of the context's pool) a second
+ *     kernel sums: integer sums, exact in any order, so the cells do not depend on the split (knob "overlap_splits").
+ *     Every cell is stored once by one lane; no atomics; no floating point;
+ *   - before and after kwage_group_finalize; both groups are only read;
+ *   - flags: KWAGE_SEARCH_TIMING fills stats->kernel_ms with the HIP-event duration of the kernels; other bits are
+ *     ignored.  stats may be NULL.
+ * The host form computes the cells in a block of the context's pool and copies them out with one strided copy.
+ * Errors, all found before a kernel runs or a byte is allocated -- cells and *stats are not written -- in this order:
+ * KWAGE_ERR_ARG for a NULL a or cells; a NULL list with a nonzero count or a list with a zero count (a's, then b's); a
+ * NULL b with cols_b; groups of different contexts; a sparse group on either side; kmer_len, num_hash, log_2_filter_len
+ * or hash_func differing; log_2_filter_len == 32 (a count of 2^32 does not fit a cell); row_elems smaller than the cells of
+ * a row; then KWAGE_ERR_STATE while a search is pending on the context; then KWAGE_ERR_ARG again for a listed column at or
+ * beyond its group's span or a pad or retired column (the first offender in list order, a's list before b's); a launch
+ * that does not fit a grid; then the pool's error (KWAGE_ERR_DEVICE), with the number of bytes needed, where the tables,
+ * the partial sums or the host form's block cannot be had.  An empty group with NULL lists writes nothing and succeeds.
+ * Synchronous; runs on the context's first stream. */
+typedef struct {
+	uint64_t n_a, n_b, rows;          /* cells are n_a x n_b, summed over rows = 2^L            */
+	uint64_t tiles, splits;           /* workgroup tiles computed; parts the row range was cut in */
+	uint64_t straight_blocks, gathered_blocks;   /* 32-column blocks of either kind               */
+	uint32_t symmetric;               /* 1: only tiles on or above the diagonal were computed   */
+	float kernel_ms;                  /* with KWAGE_SEARCH_TIMING, else 0                       */
+} kwage_overlap_stats;
+int kwage_group_column_overlaps_device(kwage_group *a, const uint64_t *cols_a, uint32_t n_a, kwage_group *b, const uint64_t *cols_b, uint32_t n_b,
+                                       void *cells_dev, uint64_t row_elems, uint32_t flags, kwage_overlap_stats *stats);
+int kwage_group_column_overlaps(kwage_group *a, const uint64_t *cols_a, uint32_t n_a, kwage_group *b, const uint64_t *cols_b, uint32_t n_b,
+                                uint32_t *cells, uint64_t row_elems, uint32_t flags, kwage_overlap_stats *stats);
+/* Which kernels the calling thread's last overlap call launched: "overlap_mfma_kernel" or
+ * "overlap_mfma_kernel+overlap_combine_kernel"; "" if none.  Valid until the thread's next one. */
+const char *kwage_group_overlap_kernel(void);
+
 /* ------------------------------------------------------------------------------------
  * Query batch: raw sequences (any case, any characters -- exactly what the reference hands to
  * search(), kwage.cpp:119,137), concatenated, uploaded once and kept resident in HBM.

@@ -66,6 +66,8 @@ struct Tuning {
 	int64_t group_contiguous = 1;   // KWAGE_GROUP_CONTIGUOUS: ask for a physically contiguous block first (0: plain hipMalloc)
 	int64_t group_placement_probe = 1;  // KWAGE_GROUP_PLACEMENT_PROBE: where two candidate blocks fit, time the gather pattern on both and keep the
 	                                //   faster (+3-4 % at C2's shape); releasing the other costs ~3 s per 100 GB (the driver wipes it), so one-shot programs turn it off
+	// the overlap matrix (overlap_plan.hpp overlap_choose_splits)
+	int64_t overlap_splits = 0;     // KWAGE_OVERLAP_SPLITS: parts the row range is cut into (0 = the plan's choice; tests: 1, 2, 3 and 8 parts of 1024 rows)
 };
 
 }  // namespace kwage

@@ -296,6 +296,53 @@ class Group:
         self._inserted(first.value, int(st.sets))
         return first.value, {f: getattr(st, f) for f, _ in native.UnionStats._fields_}
 
+    def _overlap_lists(self, cols, other, other_cols):
+        """The lists of an overlap call as the C ABI takes them: (a's pointer, n_a, b's handle, b's pointer, n_b, cells
+        [rows, columns], what the pointers point to)."""
+        if other is None and other_cols is not None:
+            raise ValueError("column_overlaps: other_cols without other (the symmetric form takes cols on both sides)")
+        keep = [None if x is None else np.ascontiguousarray(x, dtype=np.uint64).reshape(-1) for x in (cols, other_cols)]
+        ptr = [None if x is None else x.ctypes.data_as(C.c_void_p) for x in keep]      # (an empty list is refused: the pointer is not NULL)
+        n = [0 if x is None else int(x.size) for x in keep]
+        n_a = self.column_span if cols is None else n[0]
+        n_b = n_a if other is None else other.column_span if other_cols is None else n[1]
+        return ptr[0], n[0], (other._h if other is not None else None), ptr[1], n[1], (n_a, n_b), keep
+
+    def column_overlaps(self, cols: Optional[Sequence[int]] = None, other: Optional["Group"] = None, other_cols: Optional[Sequence[int]] = None,
+                        out=None, timing: bool = False):
+        """The overlap matrix (kwage_group_column_overlaps_device): cell (i, j) = the rows in which column cols[i] of this
+        group and column other_cols[j] of `other` are both set, as an integer matrix product on the matrix cores.  A list
+        of None means every column of the span (dead columns give zeros); other=None is the symmetric form, cols against
+        itself, of which only the upper tiles are computed.  Returns (cells, stats): cells an int32 device tensor
+        [len(cols), len(other_cols)] holding the uint32 counts -- `out` where given (its columns beyond the cells are
+        left alone)."""
+        import torch
+        pa, na, hb, pb, nb, (rows, width), keep = self._overlap_lists(cols, other, other_cols)
+        if out is None:
+            out = torch.empty((rows, width), dtype=torch.int32, device="cuda:%d" % self.ctx.device)
+        _device_tensor(out, "out", torch.int32, row_multiple=1)
+        if out.dim() != 2 or out.shape[0] != rows or out.shape[1] < width:
+            raise ValueError("out: shape [%d, >= %d] required, got %s" % (rows, width, tuple(out.shape)))
+        row_elems = out.stride(0) if out.shape[0] > 1 else max(out.shape[1], width)
+        st = native.OverlapStats()
+        # (an empty matrix has no address: the call refuses a NULL pointer and writes nothing through this one)
+        check(lib().kwage_group_column_overlaps_device(self._h, pa, na, hb, pb, nb, out.data_ptr() or 1, row_elems, SEARCH_TIMING if timing else 0, C.byref(st)))
+        stats = {f: getattr(st, f) for f, _ in native.OverlapStats._fields_}
+        stats["kernel"] = (lib().kwage_group_overlap_kernel() or b"").decode()
+        return out, stats
+
+    def column_overlaps_host(self, cols: Optional[Sequence[int]] = None, other: Optional["Group"] = None, other_cols: Optional[Sequence[int]] = None,
+                             timing: bool = False):
+        """column_overlaps() through the host form (kwage_group_column_overlaps): (uint32 numpy [len(cols), len(other_cols)],
+        stats)."""
+        pa, na, hb, pb, nb, (rows, width), keep = self._overlap_lists(cols, other, other_cols)
+        out = np.zeros((rows, width), dtype=np.uint32)
+        st = native.OverlapStats()
+        check(lib().kwage_group_column_overlaps(self._h, pa, na, hb, pb, nb, out.ctypes.data if out.size else 1, max(width, 1), SEARCH_TIMING if timing else 0, C.byref(st)))
+        stats = {f: getattr(st, f) for f, _ in native.OverlapStats._fields_}
+        stats["kernel"] = (lib().kwage_group_overlap_kernel() or b"").decode()
+        return out, stats
+
     @staticmethod
     def _save_columns(columns: Sequence[int], sources: Sequence):
         """The kwage_save_column array of save_db() and export_bloom_files(): (array, what its entries point to -- to be
@@ -1393,6 +1440,53 @@ class FileDatabase(Database):
                     rec.append((self._accession(path, c - first + f0), path, c - first + f0, sh, fb, cb, jv))
                 result[i] = (accessions[i], rec)
         return result
+
+    def sample_overlaps(self, accessions: Optional[Sequence[str]] = None, jaccard: bool = False) -> Tuple[List[str], np.ndarray]:
+        """The shared set bits of every pair of the chosen samples (all samples where accessions is None, in report order;
+        an accession is the first (file, column) carrying it, one not found raises KeyError): Group.column_overlaps within
+        a group in its symmetric form, between two groups of the same parameters in the a x b form, mirrored here.  Samples
+        of groups whose parameters differ from the first chosen sample's are left out -- their filters are not comparable
+        -- and named in a warning.  Returns (accessions, matrix): uint32 counts, the diagonal a sample's own bits; with
+        jaccard=True float64 shared / (bits_i + bits_j - shared), 0 where that union is empty."""
+        import warnings
+        samples = [(gi, col, self._accession(path, c)) for gi, col, path, c in self._samples()]
+        if accessions is not None:
+            found = {}
+            for gi, col, acc in samples:
+                found.setdefault(acc, (gi, col, acc))
+            for a in accessions:
+                if a not in found:
+                    raise KeyError("no sample with run accession %s in the database" % a)
+            samples = [found[a] for a in accessions]
+        if not samples:
+            return [], np.zeros((0, 0), dtype=np.float64 if jaccard else np.uint32)
+        key = lambda p: (p.kmer_len, p.num_hash, p.log_2_filter_len, p.hash_func)
+        want = key(self.groups[samples[0][0]].params)
+        left_out = [acc for gi, _, acc in samples if key(self.groups[gi].params) != want]
+        if left_out:
+            warnings.warn("sample_overlaps: %d samples of groups with other parameters are left out: %s" % (len(left_out), ", ".join(left_out)))
+        samples = [s for s in samples if key(self.groups[s[0]].params) == want]
+        n = len(samples)
+        out = np.zeros((n, n), dtype=np.uint32)
+        by_group = {}
+        for i, (gi, col, _) in enumerate(samples):
+            by_group.setdefault(gi, []).append(i)
+        gis = sorted(by_group)
+        for x, ga in enumerate(gis):
+            ia = np.array(by_group[ga])
+            ca = [samples[i][1] for i in ia]
+            out[np.ix_(ia, ia)] = self.groups[ga].column_overlaps_host(ca)[0]
+            for gb in gis[x + 1:]:
+                ib = np.array(by_group[gb])
+                cells = self.groups[ga].column_overlaps_host(ca, self.groups[gb], [samples[i][1] for i in ib])[0]
+                out[np.ix_(ia, ib)] = cells
+                out[np.ix_(ib, ia)] = cells.T
+        names = [acc for _, _, acc in samples]
+        if not jaccard:
+            return names, out
+        sh, bits = out.astype(np.int64), np.diag(out).astype(np.int64)
+        union = bits[:, None] + bits[None, :] - sh
+        return names, np.where(union > 0, sh.astype(np.float64) / np.maximum(union, 1).astype(np.float64), 0.0)
 
     def close(self) -> None:
         for d in self._info.values():

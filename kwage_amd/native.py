@@ -105,6 +105,11 @@ class UnionStats(C.Structure):
                 ("first_unit", C.c_uint64), ("units", C.c_uint64), ("bytes_written", C.c_uint64), ("kernel_ms", C.c_float)]
 
 
+class OverlapStats(C.Structure):
+    _fields_ = [("n_a", C.c_uint64), ("n_b", C.c_uint64), ("rows", C.c_uint64), ("tiles", C.c_uint64), ("splits", C.c_uint64),
+                ("straight_blocks", C.c_uint64), ("gathered_blocks", C.c_uint64), ("symmetric", C.c_uint32), ("kernel_ms", C.c_float)]
+
+
 class BloomCounterStats(C.Structure):
     _fields_ = [("num_valid_kmer", C.c_uint64), ("num_bp", C.c_uint64), ("positions", C.c_uint64),
                 ("occurrences_committed", C.c_uint64), ("chunks", C.c_uint64), ("rounds", C.c_uint64),
@@ -174,6 +179,9 @@ _SIGNATURES = [
     ("kwage_group_fold", C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(_P), C.POINTER(FoldStats)]),
     ("kwage_group_copy_columns", C.c_int, [_P, _P, _P, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(CopyStats)]),
     ("kwage_group_union_columns", C.c_int, [_P, _P, _P, _P, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(UnionStats)]),
+    ("kwage_group_column_overlaps_device", C.c_int, [_P, _P, C.c_uint32, _P, _P, C.c_uint32, _P, C.c_uint64, C.c_uint32, C.POINTER(OverlapStats)]),
+    ("kwage_group_column_overlaps", C.c_int, [_P, _P, C.c_uint32, _P, _P, C.c_uint32, _P, C.c_uint64, C.c_uint32, C.POINTER(OverlapStats)]),
+    ("kwage_group_overlap_kernel", C.c_char_p, []),
     ("kwage_batch_create", C.c_int, [_P, C.c_char_p, _P, C.c_uint32, C.POINTER(_P)]),
     ("kwage_batch_destroy", None, [_P]),
     ("kwage_batch_num_queries", C.c_uint32, [_P]),
