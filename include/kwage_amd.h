@@ -445,6 +445,70 @@ int kwage_group_column_overlaps(kwage_group *a, const uint64_t *cols_a, uint32_t
  * "overlap_mfma_kernel+overlap_combine_kernel"; "" if none.  Valid until the thread's next one. */
 const char *kwage_group_overlap_kernel(void);
 
+/* Nearest-neighbour lists, no counterpart in the reference: for every listed column of a its k best partners among the
+ * listed columns of b, chosen ON THE DEVICE from the overlap matrix's cells.  The cells are computed strip by strip of
+ * a's list by the overlap kernels into one block of the context's pool and discarded as soon as a strip's rows have been
+ * reduced to k records each: what leaves the device is n_a x k records of 16 bytes, never n_a x n_b cells.
+ *   - lists and groups exactly as kwage_group_column_overlaps takes them: any order, repeats allowed, NULL with count 0 =
+ *     every column of the span, b == NULL = a's list is also the candidate list, b may be a or another group of the
+ *     context with the same parameters; before and after finalize; both groups are only read;
+ *   - candidate j (place j of b's list; column j under a NULL list) is ELIGIBLE for entry i of a's list iff its column is
+ *     live (valid mask), entry i's column is live, shared(i, j) >= min_shared, and -- with KWAGE_NEIGHBORS_SKIP_SELF in
+ *     flags and b NULL or == a -- it does not name the same COLUMN as entry i (every repeat of that column among the
+ *     candidates is skipped; with another group as b the flag has no effect);
+ *   - a record is {index = j, shared = the overlap cell, bits_a, bits_b = the set bits of the two columns
+ *     (kwage_group_column_bits' values)};
+ *   - order: key descending, then index ascending, EXACT.  KWAGE_NEIGHBORS_SHARED: key = shared.
+ *     KWAGE_NEIGHBORS_JACCARD: the order of the fractions shared / (bits_a + bits_b - shared) -- s1 u2 > s2 u1 in 64-bit
+ *     integers -- with an empty union counting as 0; never a float.  (On the device the scalar key is
+ *     floor(shared 2^64 / union), all ones where shared == union: two distinct fractions with denominators <= 2^32 differ
+ *     by at least 2^-64, so it is strictly monotone in the fraction.);
+ *   - counts[i] = min(k, eligible candidates of entry i); out[i*k + r], r < counts[i], is the r-th best record; every
+ *     record with r >= counts[i] is {0xFFFFFFFF, 0, 0, 0}.  All n_a x k records and n_a counts are written, each once;
+ *     nothing has to be cleared beforehand, nothing else is touched.  out_dev and counts_dev are 4-byte aligned;
+ *   - 1 <= k <= KWAGE_TOPK_MAX;
+ *   - a's list is cut into STRIPS of strip_entries entries: the largest multiple of 128 whose cells -- a row of cells is
+ *     the candidates rounded up to a multiple of 4 -- fit the knob "neighbors_strip_bytes" (default 256 MiB), at least 128
+ *     and at most n_a.  Per strip the overlap kernels run in the a x b form (the symmetric saving is not used), then
+ *     neighbors_select_kernel: one workgroup per entry, an 8-bit radix select over (key, index) with histograms in LDS,
+ *     the winners ordered by a bitonic sort.  No global atomics, no floating point.  The result does not depend on the
+ *     strips or on "overlap_splits";
+ *   - flags: KWAGE_SEARCH_TIMING fills stats->kernel_ms with the HIP-event duration of the overlap and select kernels of
+ *     all strips; KWAGE_NEIGHBORS_SKIP_SELF; other bits are ignored.  stats may be NULL.
+ * The host form writes to blocks of the pool and copies records and counts out.
+ * Errors, all found before a kernel runs or a byte is allocated -- out, counts and *stats are not written -- in this
+ * order: KWAGE_ERR_ARG for a NULL a, out or counts; k out of range; an unknown metric; then every refusal of
+ * kwage_group_column_overlaps from "a NULL list with a nonzero count" on, in its order and wording (there is no row_elems);
+ * then the pool's error (KWAGE_ERR_DEVICE) with the bytes asked for.  An empty a-list (an empty group with a NULL list)
+ * writes nothing and succeeds; an empty candidate side gives counts of 0 and filler records.
+ * Synchronous; runs on the context's first stream. */
+#define KWAGE_NEIGHBORS_SHARED   0u   /* key = shared */
+#define KWAGE_NEIGHBORS_JACCARD  1u   /* key = shared / (bits_a + bits_b - shared), 0 where that union is empty */
+#define KWAGE_NEIGHBORS_SKIP_SELF 0x100u   /* in flags */
+typedef struct { uint32_t index, shared, bits_a, bits_b; } kwage_neighbor;   /* 16 bytes */
+typedef struct {
+	uint64_t n_a, n_b, rows;
+	uint64_t strips, strip_entries;   /* strips of a's list; entries of a full strip (a multiple of 128, or n_a) */
+	uint64_t tiles;                   /* overlap tiles computed, all strips together */
+	uint64_t records;                 /* sum of counts */
+	uint32_t metric;
+	float kernel_ms;                  /* with KWAGE_SEARCH_TIMING: overlap + select kernels of all strips, else 0 */
+} kwage_neighbors_stats;              /* 64 bytes */
+int kwage_group_column_neighbors_device(kwage_group *a, const uint64_t *cols_a, uint32_t n_a, kwage_group *b, const uint64_t *cols_b, uint32_t n_b,
+                                        uint32_t k, uint32_t metric, uint32_t min_shared, void *out_dev, void *counts_dev, uint32_t flags,
+                                        kwage_neighbors_stats *stats);
+int kwage_group_column_neighbors(kwage_group *a, const uint64_t *cols_a, uint32_t n_a, kwage_group *b, const uint64_t *cols_b, uint32_t n_b,
+                                 uint32_t k, uint32_t metric, uint32_t min_shared, kwage_neighbor *out, uint32_t *counts, uint32_t flags,
+                                 kwage_neighbors_stats *stats);
+/* The kernels of the strips the calling thread's last neighbours call launched -- the stages KWAGE_SEARCH_TIMING times:
+ * "overlap_mfma_kernel+neighbors_select_kernel", "overlap_mfma_kernel+overlap_combine_kernel+neighbors_select_kernel" where
+ * a strip's row range was cut into parts, "neighbors_select_kernel" alone where the candidate side is empty; "" if none.
+ * The string does not name neighbors_bits_kernel and neighbors_bits_sum_kernel, which every call with a non-empty a-list
+ * runs once beforehand, outside the timed section: they count the set bits of EVERY column of either group's span,
+ * however few are listed (kwage_group_column_bits_device refuses a group that is not finalized; this call does not).
+ * Valid until the thread's next one. */
+const char *kwage_group_neighbors_kernel(void);
+
 /* ------------------------------------------------------------------------------------
  * Query batch: raw sequences (any case, any characters -- exactly what the reference hands to
  * search(), kwage.cpp:119,137), concatenated, uploaded once and kept resident in HBM.

@@ -41,7 +41,7 @@ static const TuningName TUNING_NAMES[] = {
 	{"count_walk_min_rows", &Tuning::count_walk_min_rows},
 	{"hit_sort_host", &Tuning::hit_sort_host}, {"hit_copy_piece_kb", &Tuning::hit_copy_piece_kb}, {"shared_table_log2", &Tuning::shared_table_log2},
 	{"ext_launch_events", &Tuning::ext_launch_events}, {"group_contiguous", &Tuning::group_contiguous}, {"group_placement_probe", &Tuning::group_placement_probe},
-	{"overlap_splits", &Tuning::overlap_splits},
+	{"overlap_splits", &Tuning::overlap_splits}, {"neighbors_strip_bytes", &Tuning::neighbors_strip_bytes},
 };
 
 namespace kwage {

@@ -19,26 +19,29 @@
 
 #include "engine_state.hpp"
 #include "overlap_kernels.hpp"
+#include "overlap_launch.hpp"
 #include "overlap_plan.hpp"
 #include "pool_blocks.hpp"
 
 using namespace kwage;
 
 namespace kwage {
+
+// The kernels of one product queued on s (overlap_launch.hpp): the tiles of every part, then -- several parts -- their sum.
+int overlap_launch(hipStream_t s, const OverlapArgs &args)
+{
+	hipLaunchKernelGGL(overlap_mfma_kernel, dim3((uint32_t)((uint64_t)args.n_tiles*args.splits)), dim3(OVERLAP_THREADS), 0, s, args);
+	HIP_TRY(hipGetLastError());
+	if(args.splits > 1){
+		hipLaunchKernelGGL(overlap_combine_kernel, dim3((uint32_t)((uint64_t)args.n_tiles*(OVERLAP_TILE_CELLS/OVERLAP_THREADS))), dim3(OVERLAP_THREADS), 0, s, args);
+		HIP_TRY(hipGetLastError());
+	}
+	return KWAGE_OK;
+}
+
 namespace {
 
 thread_local char last_kernel[64] = "";
-
-CopySide side_of(const kwage_group *g) { return CopySide{g->ctx, g->d_row_map != nullptr, g->params}; }
-
-// The block of a call that cannot be had: the pool's error with the size that was asked for.
-template <typename T>
-int take_or_say(PoolBlocks &blocks, const char *who, const char *what, uint64_t bytes, T **out)
-{
-	const int rc = blocks.take(bytes, out);
-	if(rc){ return fail(rc, "%s: no device memory for the %llu bytes of %s", who, (unsigned long long)bytes, what); }
-	return KWAGE_OK;
-}
 
 int run_overlaps(const char *who, kwage_group *a, const uint64_t *cols_a, uint32_t n_a, kwage_group *b, const uint64_t *cols_b, uint32_t n_b,
                  void *cells, uint64_t row_elems, uint32_t flags, kwage_overlap_stats *stats, bool host_form)
@@ -49,11 +52,11 @@ int run_overlaps(const char *who, kwage_group *a, const uint64_t *cols_a, uint32
 	// (no group is looked into while a refusal that needs none is due)
 	const bool look = a && cells && (cols_a != nullptr) == (n_a != 0) && (cols_b != nullptr) == (n_b != 0) && (b || !cols_b);
 	if(look){
-		sa = side_of(a);
+		sa = overlap_side_of(a);
 		call.span_a = a->next_byte*8;
 		for(int i = 0; i < 2; ++i){ call.search_pending = call.search_pending || a->ctx->slot[i].busy; }
 	}
-	if(look && b){ sb = side_of(b); call.span_b = b->next_byte*8; }
+	if(look && b){ sb = overlap_side_of(b); call.span_b = b->next_byte*8; }
 	int rc = overlap_refusal(who, a ? &sa : nullptr, b ? &sb : nullptr, call);
 	if(rc){ return rc; }
 	kwage_ctx *ctx = a->ctx;
@@ -96,13 +99,7 @@ int run_overlaps(const char *who, kwage_group *a, const uint64_t *cols_a, uint32
 		};
 		if((rc = body())){ return settle(ctx, rc); }
 		rc = timed_section((flags & KWAGE_SEARCH_TIMING) != 0, ctx->stream, &kernel_ms, [&]() -> int {
-			hipLaunchKernelGGL(overlap_mfma_kernel, dim3((uint32_t)(n_tiles*plan.splits)), dim3(OVERLAP_THREADS), 0, ctx->stream, args);
-			HIP_TRY(hipGetLastError());
-			if(plan.splits > 1){
-				hipLaunchKernelGGL(overlap_combine_kernel, dim3((uint32_t)(n_tiles*(OVERLAP_TILE_CELLS/OVERLAP_THREADS))), dim3(OVERLAP_THREADS), 0, ctx->stream, args);
-				HIP_TRY(hipGetLastError());
-			}
-			return KWAGE_OK;
+			return overlap_launch(ctx->stream, args);
 		});
 		if(rc){ return settle(ctx, rc); }
 		if(host_form){

@@ -19,21 +19,6 @@ constexpr uint32_t OVERLAP_LDS_BLOCK = OVERLAP_STEP_GROUPS*OVERLAP_LDS_PITCH;
 typedef int overlap_v4i __attribute__((ext_vector_type(4)));
 typedef int overlap_v16i __attribute__((ext_vector_type(16)));
 
-struct OverlapArgs {
-	const uint8_t *a_bits, *b_bits;
-	unsigned long long a_stride, b_stride;
-	unsigned long long rows, groups;           // rows of both matrices; groups of 32 rows
-	const OverlapBlock *blocks_a, *blocks_b;   // overlap_plan.hpp (symmetric: the same table)
-	uint32_t n_blocks_a, n_blocks_b;
-	const OverlapTile *tiles;
-	uint32_t n_tiles, splits;
-	unsigned long long n_a, n_b;               // cells: n_a x n_b
-	uint32_t symmetric;
-	uint32_t *cells;
-	unsigned long long row_elems;
-	uint32_t *partial;                         // splits > 1: [part][tile][128][128]
-};
-
 // Cell (ia, jb) of the result, and in the symmetric form its mirror for a tile above the diagonal: one store each, by
 // the one lane that holds the sum.
 __device__ __forceinline__ void overlap_store_cell(const OverlapArgs &p, bool mirror, uint64_t ia, uint64_t jb, uint32_t v)

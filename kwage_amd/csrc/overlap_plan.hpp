@@ -45,6 +45,22 @@ struct OverlapPlan {
 	std::vector<OverlapTile> tiles;
 };
 
+// What a launch of the kernels (overlap_kernels.hpp) is told: plain values, filled by overlap.hip and neighbors.hip.
+struct OverlapArgs {
+	const uint8_t *a_bits, *b_bits;
+	unsigned long long a_stride, b_stride;
+	unsigned long long rows, groups;           // rows of both matrices; groups of 32 rows
+	const OverlapBlock *blocks_a, *blocks_b;   // overlap_plan.hpp (symmetric: the same table)
+	uint32_t n_blocks_a, n_blocks_b;
+	const OverlapTile *tiles;
+	uint32_t n_tiles, splits;
+	unsigned long long n_a, n_b;               // cells: n_a x n_b
+	uint32_t symmetric;
+	uint32_t *cells;
+	unsigned long long row_elems;
+	uint32_t *partial;                         // splits > 1: [part][tile][128][128]
+};
+
 // What the refusals need to know of a call besides the two sides (copy_plan.hpp CopySide).
 struct OverlapCall {
 	bool have_cells, have_cols_a, have_cols_b;

@@ -68,6 +68,8 @@ struct Tuning {
 	                                //   faster (+3-4 % at C2's shape); releasing the other costs ~3 s per 100 GB (the driver wipes it), so one-shot programs turn it off
 	// the overlap matrix (overlap_plan.hpp overlap_choose_splits)
 	int64_t overlap_splits = 0;     // KWAGE_OVERLAP_SPLITS: parts the row range is cut into (0 = the plan's choice; tests: 1, 2, 3 and 8 parts of 1024 rows)
+	// the nearest-neighbour lists (neighbors_plan.hpp neighbors_strip_entries)
+	int64_t neighbors_strip_bytes = 256ll << 20;   // KWAGE_NEIGHBORS_STRIP_BYTES: the cells of a strip of a's list fit this many bytes (tests: several strips)
 };
 
 }  // namespace kwage

@@ -343,6 +343,52 @@ class Group:
         stats["kernel"] = (lib().kwage_group_overlap_kernel() or b"").decode()
         return out, stats
 
+    _NEIGHBOR_METRICS = {"shared": 0, "jaccard": 1}           # KWAGE_NEIGHBORS_SHARED, KWAGE_NEIGHBORS_JACCARD
+    _NEIGHBORS_SKIP_SELF = 0x100                              # KWAGE_NEIGHBORS_SKIP_SELF
+
+    def _neighbor_call(self, k, cols, other, other_cols, metric, min_shared, skip_self, timing):
+        if other is None and other_cols is not None:
+            raise ValueError("column_neighbors: other_cols without other (cols is then the candidate list as well)")
+        if metric not in self._NEIGHBOR_METRICS:
+            raise ValueError("column_neighbors: metric must be 'jaccard' or 'shared', got %r" % (metric,))
+        pa, na, hb, pb, nb, (rows, _), keep = self._overlap_lists(cols, other, other_cols)
+        flags = (SEARCH_TIMING if timing else 0) | (self._NEIGHBORS_SKIP_SELF if skip_self else 0)
+        return (pa, na, hb, pb, nb, int(k), self._NEIGHBOR_METRICS[metric], int(min_shared)), flags, rows, keep
+
+    @staticmethod
+    def _neighbor_stats(st):
+        stats = {f: getattr(st, f) for f, _ in native.NeighborsStats._fields_}
+        stats["kernel"] = (lib().kwage_group_neighbors_kernel() or b"").decode()
+        return stats
+
+    def column_neighbors(self, k: int, cols: Optional[Sequence[int]] = None, other: Optional["Group"] = None, other_cols: Optional[Sequence[int]] = None,
+                         metric: str = "jaccard", min_shared: int = 0, skip_self: bool = False, timing: bool = False):
+        """Nearest-neighbour lists (kwage_group_column_neighbors_device): for every column of `cols` its k best partners among
+        `other_cols` of `other` (cols itself where other is None), by Jaccard index or by shared set bits, in the exact order
+        (key descending, index ascending), chosen on the device from the overlap matrix's cells strip by strip.  Lists as
+        column_overlaps() takes them.  Returns (records, counts, stats): int32 device tensors [n_a, k, 4] -- (index, shared,
+        bits of the column, bits of the partner) as uint32, (0xFFFFFFFF, 0, 0, 0) behind counts[i] -- and [n_a]."""
+        import torch
+        args, flags, rows, keep = self._neighbor_call(k, cols, other, other_cols, metric, min_shared, skip_self, timing)
+        dev = "cuda:%d" % self.ctx.device
+        records = torch.empty((rows, max(int(k), 0), 4), dtype=torch.int32, device=dev)
+        counts = torch.empty((rows,), dtype=torch.int32, device=dev)
+        st = native.NeighborsStats()
+        # (an empty result has no address: the call refuses a NULL pointer and writes nothing through this one)
+        check(lib().kwage_group_column_neighbors_device(self._h, *args, records.data_ptr() or 1, counts.data_ptr() or 1, flags, C.byref(st)))
+        return records, counts, self._neighbor_stats(st)
+
+    def column_neighbors_host(self, k: int, cols: Optional[Sequence[int]] = None, other: Optional["Group"] = None, other_cols: Optional[Sequence[int]] = None,
+                              metric: str = "jaccard", min_shared: int = 0, skip_self: bool = False, timing: bool = False):
+        """column_neighbors() through the host form (kwage_group_column_neighbors): (uint32 numpy [n_a, k, 4], uint32 numpy
+        [n_a], stats)."""
+        args, flags, rows, keep = self._neighbor_call(k, cols, other, other_cols, metric, min_shared, skip_self, timing)
+        records = np.zeros((rows, max(int(k), 0), 4), dtype=np.uint32)
+        counts = np.zeros((rows,), dtype=np.uint32)
+        st = native.NeighborsStats()
+        check(lib().kwage_group_column_neighbors(self._h, *args, records.ctypes.data if records.size else 1, counts.ctypes.data if counts.size else 1, flags, C.byref(st)))
+        return records, counts, self._neighbor_stats(st)
+
     @staticmethod
     def _save_columns(columns: Sequence[int], sources: Sequence):
         """The kwage_save_column array of save_db() and export_bloom_files(): (array, what its entries point to -- to be
@@ -1487,6 +1533,56 @@ class FileDatabase(Database):
         sh, bits = out.astype(np.int64), np.diag(out).astype(np.int64)
         union = bits[:, None] + bits[None, :] - sh
         return names, np.where(union > 0, sh.astype(np.float64) / np.maximum(union, 1).astype(np.float64), 0.0)
+
+    def sample_neighbors(self, k: int, accessions: Optional[Sequence[str]] = None, metric: str = "jaccard", min_shared: int = 0,
+                         skip_self: bool = True) -> List[Tuple[str, List[Tuple[str, str, int, int, int, int, float]]]]:
+        """Per chosen sample (every sample where accessions is None, in report order; an accession is the first (file,
+        column) carrying it, one not found raises KeyError) its k most similar samples of the database, chosen on the
+        device (Group.column_neighbors_host, one call per pair of query group and candidate group) and merged here under
+        the same exact order -- the Jaccard index as a fraction, or the shared bits -- with ties in database order (group,
+        then column).  The candidates are every sample of every resident group whose parameters equal the first chosen
+        sample's; the samples of other groups are left out and named in a warning.  Returns
+        [(accession, [(neighbour accession, path, column in the file, shared, query_bits, neighbour_bits, jaccard), ...]), ...]."""
+        import warnings
+        from fractions import Fraction
+        every = [(gi, col, path, c, self._accession(path, c)) for gi, col, path, c in self._samples()]
+        queries = every
+        if accessions is not None:
+            found = {}
+            for s in every:
+                found.setdefault(s[4], s)
+            for a in accessions:
+                if a not in found:
+                    raise KeyError("no sample with run accession %s in the database" % a)
+            queries = [found[a] for a in accessions]
+        if not queries:
+            return []
+        key = lambda p: (p.kmer_len, p.num_hash, p.log_2_filter_len, p.hash_func)
+        want = key(self.groups[queries[0][0]].params)
+        left_out = [s[4] for s in every if key(self.groups[s[0]].params) != want]
+        if left_out:
+            warnings.warn("sample_neighbors: %d samples of groups with other parameters are left out: %s" % (len(left_out), ", ".join(left_out)))
+        queries = [s for s in queries if key(self.groups[s[0]].params) == want]
+        cands = {}                                            # group -> [(place in the database, sample)]
+        for place, s in enumerate(every):
+            if key(self.groups[s[0]].params) == want:
+                cands.setdefault(s[0], []).append((place, s))
+        by_group = {}
+        for i, s in enumerate(queries):
+            by_group.setdefault(s[0], []).append(i)
+        lists = [[] for _ in queries]
+        for ga in sorted(by_group):
+            mine = by_group[ga]
+            for gb in sorted(cands):
+                rec, cnt, _ = self.groups[ga].column_neighbors_host(k, [queries[i][1] for i in mine], self.groups[gb], [s[1] for _, s in cands[gb]],
+                                                                    metric=metric, min_shared=min_shared, skip_self=skip_self)
+                for q, i in enumerate(mine):
+                    for index, shared, bits_a, bits_b in rec[q, :cnt[q]].tolist():
+                        union = bits_a + bits_b - shared
+                        order = shared if metric == "shared" else (Fraction(shared, union) if union else Fraction(0))
+                        place, s = cands[gb][index]
+                        lists[i].append((-order, place, (s[4], s[2], s[3], shared, bits_a, bits_b, shared / union if union else 0.0)))
+        return [(queries[i][4], [t[2] for t in sorted(lists[i], key=lambda t: t[:2])[:k]]) for i in range(len(queries))]
 
     def close(self) -> None:
         for d in self._info.values():

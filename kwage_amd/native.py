@@ -110,6 +110,15 @@ class OverlapStats(C.Structure):
                 ("straight_blocks", C.c_uint64), ("gathered_blocks", C.c_uint64), ("symmetric", C.c_uint32), ("kernel_ms", C.c_float)]
 
 
+class Neighbor(C.Structure):
+    _fields_ = [("index", C.c_uint32), ("shared", C.c_uint32), ("bits_a", C.c_uint32), ("bits_b", C.c_uint32)]
+
+
+class NeighborsStats(C.Structure):
+    _fields_ = [("n_a", C.c_uint64), ("n_b", C.c_uint64), ("rows", C.c_uint64), ("strips", C.c_uint64), ("strip_entries", C.c_uint64),
+                ("tiles", C.c_uint64), ("records", C.c_uint64), ("metric", C.c_uint32), ("kernel_ms", C.c_float)]
+
+
 class BloomCounterStats(C.Structure):
     _fields_ = [("num_valid_kmer", C.c_uint64), ("num_bp", C.c_uint64), ("positions", C.c_uint64),
                 ("occurrences_committed", C.c_uint64), ("chunks", C.c_uint64), ("rounds", C.c_uint64),
@@ -182,6 +191,9 @@ _SIGNATURES = [
     ("kwage_group_column_overlaps_device", C.c_int, [_P, _P, C.c_uint32, _P, _P, C.c_uint32, _P, C.c_uint64, C.c_uint32, C.POINTER(OverlapStats)]),
     ("kwage_group_column_overlaps", C.c_int, [_P, _P, C.c_uint32, _P, _P, C.c_uint32, _P, C.c_uint64, C.c_uint32, C.POINTER(OverlapStats)]),
     ("kwage_group_overlap_kernel", C.c_char_p, []),
+    ("kwage_group_column_neighbors_device", C.c_int, [_P, _P, C.c_uint32, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _P, _P, C.c_uint32, C.POINTER(NeighborsStats)]),
+    ("kwage_group_column_neighbors", C.c_int, [_P, _P, C.c_uint32, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _P, _P, C.c_uint32, C.POINTER(NeighborsStats)]),
+    ("kwage_group_neighbors_kernel", C.c_char_p, []),
     ("kwage_batch_create", C.c_int, [_P, C.c_char_p, _P, C.c_uint32, C.POINTER(_P)]),
     ("kwage_batch_destroy", None, [_P]),
     ("kwage_batch_num_queries", C.c_uint32, [_P]),
